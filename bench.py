@@ -2,14 +2,17 @@
 resize -> stitched Conv3d -> AnySplat reconstruction (13 views @512), synthetic inputs and seeded random weights of the
 production shapes (BASELINE.json configs[1]; no checkpoint is reachable offline).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...        (started as a plain process it re-launches ITSELF under torch.distributed.run, 127.0.0.1 rendezvous,
                                          a free port, one rank per GPU, and still prints the one JSON line - `spawn_ranks` below)
 
 One "step" = one complete scene.  N>1 = data parallel over prompts exactly like the reference (prompt_list[rank::world],
 /root/reference/inference_t23d.py:62): every rank owns whole scenes, no data-path collective (weak scaling).
-Rank 0 prints ONE JSON line (contract in the task statement) incl. `roofline` for the dominant kernel and `cpu_baseline`."""
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline figure; `--full` adds everything
+measured beside it: `roofline` for the dominant kernel (event-probed during the last timed scene), stage times and `stage_roofline`, the
+untimed extras (orbit render, spread-cloud tail, box speed probe, sustained clock), the sequence-parallel RCCL profile and `cpu_baseline`.
+`--dump-outputs DIR` writes what the last timed scene returned to its caller as DIR/<name>.npy (seeded inputs: identical from run to run)."""
 from __future__ import annotations
 
 import argparse
@@ -218,6 +221,52 @@ def timed_steps(step, steps: int, warmup: int, sync, world: int, reduce_max):
     return (reduce_max(dt) if world > 1 else dt), dt, out
 
 
+DUMP_BUDGET_BYTES = 56 << 20   # all --dump-outputs arrays together, well under 64 MB with the .npy headers
+
+
+def output_arrays(obj, prefix: str = "", acc=None) -> dict:
+    """{dotted name: tensor} of every tensor / number in what Text23DGS.generate returns (dataclasses, dicts and lists walked in order)."""
+    import dataclasses
+    acc = {} if acc is None else acc
+    join = (lambda k: f"{prefix}.{k}") if prefix else str
+    if torch.is_tensor(obj):
+        acc[prefix] = obj
+    elif isinstance(obj, (int, float)) and not isinstance(obj, bool):
+        acc[prefix] = torch.tensor(obj, dtype=torch.float64)
+    elif dataclasses.is_dataclass(obj):
+        for f in dataclasses.fields(obj):
+            output_arrays(getattr(obj, f.name), join(f.name), acc)
+    elif isinstance(obj, dict):
+        for k, v in obj.items():
+            output_arrays(v, join(k), acc)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            output_arrays(v, join(i), acc)
+    return acc
+
+
+def dump_outputs(arrays: dict, out_dir, budget: int = DUMP_BUDGET_BYTES, seed: int = 0) -> None:
+    """Write every array as out_dir/<name>.npy: float64 for float64 / integer tensors, float32 otherwise.  The budget is shared smallest
+    array first; an array larger than its share is replaced by a fixed, seeded sample of its flattened elements (the same sorted, distinct
+    indices on every run for the same element count)."""
+    import numpy as np
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    out_dtype = lambda t: torch.float64 if t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool) else torch.float32
+    size = lambda t: t.numel() * (8 if out_dtype(t) == torch.float64 else 4)
+    items = sorted(arrays.items(), key=lambda kv: (size(kv[1]), kv[0]))
+    for n, (name, t) in enumerate(items):
+        dt = out_dtype(t)
+        k = budget // (len(items) - n) // (8 if dt == torch.float64 else 4)
+        t = t.detach()
+        if t.numel() > k:
+            idx = torch.randint(t.numel(), (k,), generator=torch.Generator().manual_seed(seed)).unique()
+            t = t.reshape(-1)[idx.to(t.device)]
+        t = t.to(dt)
+        budget -= t.numel() * t.element_size()
+        np.save(d / f"{name}.npy", t.cpu().numpy())
+
+
 def launch_self_test(a, world: int, rank: int) -> None:
     """--launch-self-test: the rendezvous / barrier / max-over-ranks / one-line skeleton of this file on the CPU (gloo) around a stub step
     that only sleeps - what tests/test_host_logic.py runs with --gpus 2 to prove that a launcher-less `python bench.py --gpus N` comes
@@ -260,8 +309,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--denoise-steps", type=int, default=50)
     ap.add_argument("--num-frames", type=int, default=13)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline figure: dominant-kernel roofline, stage times and FLOPs, untimed extras, "
+                         "RCCL profile (--parallel scene), CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the arrays the last timed scene returned as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     ap.add_argument("--cpu-baseline", choices=["full", "dit", "none"], default="full",
-                    help="CPU oracle timed once per stage on this host (full: ~2-3 min of CPU after the timed GPU region)")
+                    help="--full only: CPU oracle timed once per stage on this host (full: ~2-3 min of CPU after the timed GPU region)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--model", choices=["1.3b", "14b"], default="1.3b",
                     help="14b = BASELINE config #4 geometry (Wan-14B, 40 x 128 heads, FFN 13824, 40 blocks); NOT the headline config")
@@ -320,9 +374,8 @@ def main():
         # the reference seeds once per process and strides prompts over ranks: scene i of this rank = global prompt i*world+rank
         g = torch.Generator().manual_seed(12413 + (i if coop else i * world + rank))
         lat0 = torch.randn(1, 16, Tl, 64, 64, generator=g)
-        out, _, _ = model.generate(pe, ne, latents=lat0, num_frames=a.num_frames, num_inference_steps=a.denoise_steps,
-                                   guidance_scale=7.5, timings=timings, stage_flops=stage_flops)
-        return out
+        return model.generate(pe, ne, latents=lat0, num_frames=a.num_frames, num_inference_steps=a.denoise_steps,
+                              guidance_scale=7.5, timings=timings, stage_flops=stage_flops)
 
     def sync():
         torch.cuda.synchronize()
@@ -333,32 +386,74 @@ def main():
     # dominant kernel = the bf16 GEMM tile every N=1536/3072/8960-wide projection resolves to (one kernel symbol)
     f8 = a.dtype == "fp8"   # then the dominant kernel is the e4m3 form of the same tile
     dom_tile = lib.load().v3a_gemm_fp8_pick_tile(2 * N, cfg.dim) if f8 else lib.load().v3a_gemm_pick_tile(2 * N, cfg.dim)
-    # every 7th launch of the symbol is bracketed by events.  Per DiT block the symbol runs FIVE times - self-attention out-projection,
-    # cross-attention to_q, the batched cached-context GEMM (two per-prompt operands in one launch), FFN2 and the two-round q|k
-    # projection - and 7 is coprime to 5, so every shape is sampled equally: 30 blocks x 5 x 50 (CFG-batched) forwards / 7 = ~1075 samples per scene,
-    # and the event pairs do not cost the probed scene 3 % of its time as bracketing every launch did
-    probe = ops.GemmProbe(dom_tile, fp8=f8, stride=7)
-    ops.set_gemm_probe(probe)
+    probe = None
+    if a.full:
+        # every 7th launch of the symbol is bracketed by events.  Per DiT block the symbol runs FIVE times - self-attention out-projection,
+        # cross-attention to_q, the batched cached-context GEMM (two per-prompt operands in one launch), FFN2 and the two-round q|k
+        # projection - and 7 is coprime to 5, so every shape is sampled equally: 30 blocks x 5 x 50 (CFG-batched) forwards / 7 = ~1075 samples per scene,
+        # and the event pairs do not cost the probed scene 3 % of its time as bracketing every launch did
+        probe = ops.GemmProbe(dom_tile, fp8=f8, stride=7)
+        ops.set_gemm_probe(probe)
     stage = SceneTimes()
 
     def step(i, last):
-        probe.active = last and i >= 0   # HIP-event pairs around the sampled launches of the dominant kernel during the last timed scene
-        return scene(i, stage if (last and i >= 0) else None)
+        measured = a.full and last and i >= 0
+        if probe is not None:
+            probe.active = measured   # HIP-event pairs around the sampled launches of the dominant kernel during the last timed scene
+        return scene(i, stage if measured else None)
 
     def reduce_max(t):
         tt = torch.tensor([t], device=dev, dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return tt.item()
 
-    dt_max, dt, out = timed_steps(step, a.steps, a.warmup, sync, world, reduce_max)
-    probe.active = False
-    ops.set_gemm_probe(None)
-    per_rank = rccl_info = None
+    dt_max, dt, (out, lat, clip) = timed_steps(step, a.steps, a.warmup, sync, world, reduce_max)
+    if probe is not None:
+        probe.active = False
+        ops.set_gemm_probe(None)
+    if a.dump_outputs and rank == 0:
+        dump_outputs({**output_arrays(out), "latents": lat, "clip": clip}, a.dump_outputs)
+    rccl_info = None
     if world > 1:
         # what torch.distributed actually ran on: a SCALE run shows the rank count / backend it saw without a code change
         rccl_info = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "gpus_visible_to_rank0": torch.cuda.device_count(),
                      "mode": "scene (CFG x sequence parallel, RCCL all-gathers on the data path)" if coop else "dp (no data-path collective)",
                      "launched_by": os.environ.get("V3A_BENCH_LAUNCHED_BY", "external launcher (torch.distributed.run)")}
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "3D Gaussian scenes/sec (50-step denoise, 512^2, 13 views)",
+            "value": (1 if coop else world) * a.steps / dt_max, "unit": "scenes/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+            "ms_per_step": dt_max / a.steps * 1e3, "higher_is_better": True, "scaling": "strong" if coop else "weak", "vs_baseline": None,
+            "dtype": {"bf16": "bf16", "fp8-attn": "fp8 (e4m3 self-attention operands; bf16 GEMMs)",
+                      "fp8": "fp8 (e4m3 self-attention and block projection / FFN GEMM operands, fp32 accumulation; bf16 elsewhere)"}[a.dtype],
+            "data": "synthetic (seeded random weights of production shapes, synthetic text embeddings)",
+            "config": {"workload": f"Wan-{'14B' if a.model == '14b' else '1.3B'} stitched, {a.denoise_steps}-step CFG denoise (batch-2 cond/uncond), {a.num_frames} views @512, "
+                                   "VAE decode, 448^2 AnySplat enc_blocks_2 reconstruction with voxel fusion; "
+                                   + ("one scene over all GPUs (CFG-parallel x sequence-parallel)" if coop else "1 prompt per GPU (data parallel)"),
+                       "denoise_steps": a.denoise_steps, "views": a.num_frames, "dit_tokens": N, "gaussians_last_scene": int(out.gaussians.means.shape[1]),
+                       "precision": {"dit / vae / recon backbone": "bf16 MFMA, fp32 accumulate (the reference's autocast dtype)",
+                                     "camera head": "fp32",
+                                     "depth + gaussian DPT heads": ("fp32-equivalent (split-bf16 MFMA: 3 products, fp32 accumulate, fp32 activations as bf16 pairs) - the reference "
+                                                                    "runs them with autocast off" if model.stitched_decoder.stitched_3d_model.engine().cfg.dpt_precision == "f32"
+                                                                    else "bf16 (opt-in deviation)")},
+                       **({"rccl": rccl_info} if rccl_info else {}),
+                       **({"scene_parallel": {
+                           "layout": dict(zip(("cfg_degree", "sp_degree"), DenoisePlan.layout(world))),
+                           "sp_mode": ("exact (sp_kv_split = 1): bit-identical to the single-GPU forward" if model.transformer.sp_kv_split == 1 else
+                                       "default (sp_kv_split = None): key-split attention + split-K FFN2 on the shards - deterministic, within bf16 "
+                                       "rounding (5e-3) of the single-GPU forward, NOT bit-identical"),
+                           "graph": ("hipGraph replay of each rank's sharded forward incl. its RCCL all-gathers (--sp-graph)" if a.sp_graph else
+                                     "eager (pass --sp-graph to replay the sharded forward from a captured hipGraph)")}} if coop else {})},
+        }
+    if not a.full:
+        if line is not None:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    per_rank = None
+    if world > 1:
         # every rank's wall time and stage times of its last scene (not part of the timed region): shows WHICH stage or rank is slow
         mine = torch.tensor([dt, stage.denoise_ms, stage.vae_ms, stage.recon_ms], device=dev, dtype=torch.float64)
         allr = torch.empty(world, 4, device=dev, dtype=torch.float64)
@@ -374,7 +469,6 @@ def main():
             for pr, v in zip(per_rank, allr.cpu().tolist()):
                 pr["recon_view_shard"] = {"views": int(v[0]), "backbone_ms": round(v[1], 1), "camera_replicated_ms": round(v[2], 1),
                                           "heads_ms": round(v[3], 1), "gather_and_tail_ms": round(v[4], 1)}
-    dt = dt_max
     comm = None
     if coop:
         # RCCL time of the sequence-parallel all-gathers on their own: two extra denoise steps, untimed, with every all-gather run
@@ -479,54 +573,32 @@ def main():
         tr = model.transformer
         ent = next(iter(tr._ctx.values()))[1] if getattr(tr, "_ctx", None) else None
         hxk = cfg.num_attention_heads * ent[8] if (ent is not None and ent[7] is not None) else 0   # cached-context form active: heads x padded keys
-        U = int(out.gaussians.means.shape[1])
         dom_symbol = SYMBOL_OF_TILE.get(lib.load().v3a_gemm_tile_name(dom_tile).decode()) if not f8 else None
         traffic, traffic_src = (None, "fp8 mode: not profiled") if f8 else (pmc_traffic(dom_symbol) if dom_symbol else (None, "unknown tile symbol"))
-        line = {
-            "metric": "3D Gaussian scenes/sec (50-step denoise, 512^2, 13 views)",
-            "value": (1 if coop else world) * a.steps / dt, "unit": "scenes/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "strong" if coop else "weak", "vs_baseline": None,
-            "dtype": {"bf16": "bf16", "fp8-attn": "fp8 (e4m3 self-attention operands; bf16 GEMMs)",
-                      "fp8": "fp8 (e4m3 self-attention and block projection / FFN GEMM operands, fp32 accumulation; bf16 elsewhere)"}[a.dtype],
-            "data": "synthetic (seeded random weights of production shapes, synthetic text embeddings)",
-            "config": {"workload": f"Wan-{'14B' if a.model == '14b' else '1.3B'} stitched, {a.denoise_steps}-step CFG denoise (batch-2 cond/uncond), {a.num_frames} views @512, "
-                                   "VAE decode, 448^2 AnySplat enc_blocks_2 reconstruction with voxel fusion; "
-                                   + ("one scene over all GPUs (CFG-parallel x sequence-parallel)" if coop else "1 prompt per GPU (data parallel)"),
-                       "denoise_steps": a.denoise_steps, "views": a.num_frames, "dit_tokens": N, "gaussians_last_scene": U,
-                       "precision": {"dit / vae / recon backbone": "bf16 MFMA, fp32 accumulate (the reference's autocast dtype)",
-                                     "camera head": "fp32",
-                                     "depth + gaussian DPT heads": ("fp32-equivalent (split-bf16 MFMA: 3 products, fp32 accumulate, fp32 activations as bf16 pairs) - the reference "
-                                                                    "runs them with autocast off" if model.stitched_decoder.stitched_3d_model.engine().cfg.dpt_precision == "f32"
-                                                                    else "bf16 (opt-in deviation)")},
-                       **({"per_rank_last_scene": per_rank, "rccl": rccl_info} if per_rank else {}),
-                       **({"scene_parallel": {
-                           "layout": dict(zip(("cfg_degree", "sp_degree"), DenoisePlan.layout(world))),
-                           "sp_mode": ("exact (sp_kv_split = 1): bit-identical to the single-GPU forward" if model.transformer.sp_kv_split == 1 else
-                                       "default (sp_kv_split = None): key-split attention + split-K FFN2 on the shards - deterministic, within bf16 "
-                                       "rounding (5e-3) of the single-GPU forward, NOT bit-identical"),
-                           "graph": ("hipGraph replay of each rank's sharded forward incl. its RCCL all-gathers (--sp-graph)" if a.sp_graph else
-                                     "eager (pass --sp-graph to replay the sharded forward from a captured hipGraph)"),
-                           "rccl_all_gather (2 untimed profiled steps, collectives serialised)": comm}} if coop else {}),
-                       "stage_ms_last_scene": {"denoise": round(stage.denoise_ms, 1), "vae_decode+resize": round(stage.vae_ms, 1),
-                                               "stitch+recon": round(stage.recon_ms, 1)},
-                       "orbit_render_ms_132_cameras_448 (untimed extra)": round(render_ms, 1),
-                       "recon_tail_on_spread_cloud (untimed extra)": tail,
-                       "box_speed_probe (untimed extra)": box,
-                       "dit_model_tflops_per_s": round(2 * a.denoise_steps * fwd_flops / (stage.denoise_ms * 1e-3) / 1e12, 1),
-                       "dit_executed_tflops_per_s": round(2 * a.denoise_steps * dit_flops_executed(N, cfg.dim, cfg.ffn_dim, cfg.num_layers, ctx_keys, hxk)
-                                                          / (stage.denoise_ms * 1e-3) / 1e12, 1),
-                       "dit_flops_note": f"model = BASELINE.md §2 formula (512 text keys, context K/V projected every step); executed = "
-                                         f"{ctx_keys} cross-attention keys after merging the zero-padding keys, context K/V cached per prompt"
-                                         + (f", cross-attention in the cached-context form (to_out folded into a per-prompt V.Wo^T: one GEMM with K = {hxk})" if hxk else "")},
-            "roofline": {"bound": "mfma",
-                         "kernel": (f"gemm_pp_kernel<.., F8> = tile {lib.load().v3a_gemm_fp8_tile_name(dom_tile).decode()} (e4m3 MFMA 32x32x64 f8f6f4, ping-pong)" if f8 else
-                                    f"{dom_symbol} = tile {lib.load().v3a_gemm_tile_name(dom_tile).decode()} (bf16 MFMA 32x32x16, ping-pong 256x192)"),
-                         "achieved": round(ach, 1), "peak": FP8_MFMA_PEAK_TFLOPS if f8 else BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": round(ach / (FP8_MFMA_PEAK_TFLOPS if f8 else BF16_MFMA_PEAK_TFLOPS), 4),
-                         "traffic": traffic, "traffic_unit": "bytes/launch (PMC FETCH_SIZE + WRITE_SIZE of this symbol)", "traffic_source": traffic_src,
-                         "launches_timed": ps["launches"], "launch_sampling": "every 7th launch of the symbol in the last timed scene", "avg_launch_ms": round(ps["avg_ms"], 4),
-                         "flops_per_launch": ps["flops_per_launch"]},
-        }
+        if per_rank:
+            line["config"]["per_rank_last_scene"] = per_rank
+        if coop:
+            line["config"]["scene_parallel"]["rccl_all_gather (2 untimed profiled steps, collectives serialised)"] = comm
+        line["config"].update({
+            "stage_ms_last_scene": {"denoise": round(stage.denoise_ms, 1), "vae_decode+resize": round(stage.vae_ms, 1),
+                                    "stitch+recon": round(stage.recon_ms, 1)},
+            "orbit_render_ms_132_cameras_448 (untimed extra)": round(render_ms, 1),
+            "recon_tail_on_spread_cloud (untimed extra)": tail,
+            "box_speed_probe (untimed extra)": box,
+            "dit_model_tflops_per_s": round(2 * a.denoise_steps * fwd_flops / (stage.denoise_ms * 1e-3) / 1e12, 1),
+            "dit_executed_tflops_per_s": round(2 * a.denoise_steps * dit_flops_executed(N, cfg.dim, cfg.ffn_dim, cfg.num_layers, ctx_keys, hxk)
+                                               / (stage.denoise_ms * 1e-3) / 1e12, 1),
+            "dit_flops_note": f"model = BASELINE.md §2 formula (512 text keys, context K/V projected every step); executed = "
+                              f"{ctx_keys} cross-attention keys after merging the zero-padding keys, context K/V cached per prompt"
+                              + (f", cross-attention in the cached-context form (to_out folded into a per-prompt V.Wo^T: one GEMM with K = {hxk})" if hxk else "")})
+        line["roofline"] = {"bound": "mfma",
+                            "kernel": (f"gemm_pp_kernel<.., F8> = tile {lib.load().v3a_gemm_fp8_tile_name(dom_tile).decode()} (e4m3 MFMA 32x32x64 f8f6f4, ping-pong)" if f8 else
+                                       f"{dom_symbol} = tile {lib.load().v3a_gemm_tile_name(dom_tile).decode()} (bf16 MFMA 32x32x16, ping-pong 256x192)"),
+                            "achieved": round(ach, 1), "peak": FP8_MFMA_PEAK_TFLOPS if f8 else BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                            "frac": round(ach / (FP8_MFMA_PEAK_TFLOPS if f8 else BF16_MFMA_PEAK_TFLOPS), 4),
+                            "traffic": traffic, "traffic_unit": "bytes/launch (PMC FETCH_SIZE + WRITE_SIZE of this symbol)", "traffic_source": traffic_src,
+                            "launches_timed": ps["launches"], "launch_sampling": "every 7th launch of the symbol in the last timed scene", "avg_launch_ms": round(ps["avg_ms"], 4),
+                            "flops_per_launch": ps["flops_per_launch"]}
         pk_tf = FP8_MFMA_PEAK_TFLOPS if f8 else BF16_MFMA_PEAK_TFLOPS
 
         def srow(flops, ms, note, kinds=None):

@@ -179,6 +179,21 @@ def build_reference_stitched(cfg, sd):
     return model.eval()
 
 
+def _capture_voxel_inputs(model):
+    """Record the points and confidences the reference's voxelizaton_with_fusion receives: the voxel keys are a discontinuous function
+    of the points, and coordinates that differ in the last bits between CPUs (vector ISA, thread count) land in other voxels, so the
+    tests voxelize the reference's own points and compare the continuous inputs separately (the features are too large to store; they
+    enter the fused voxels continuously and are pinned through the Gaussian parameters)."""
+    enc, seen = model.encoder, {}
+    orig = enc.voxelizaton_with_fusion
+
+    def wrapped(img_feat, pts3d, voxel_size, conf=None):
+        seen.update(vox_pts=pts3d.detach().clone(), vox_conf=conf.detach().clone())
+        return orig(img_feat, pts3d, voxel_size, conf=conf)
+    enc.voxelizaton_with_fusion = wrapped
+    return seen
+
+
 def recon_tiny():
     """The reference's AnySplatStitched.forward at reduced width (C=64) but full depth (22 DINO + 24x2 aggregator blocks),
     2 views @28x28, voxelisation active.  Pins the whole R3-R17 restatement end to end."""
@@ -186,6 +201,7 @@ def recon_tiny():
     cfg = R.ReconCfg(**RECON_TINY)
     sd = R.make_recon_weights(cfg, seed=41)
     model = build_reference_stitched(cfg, sd)
+    vox = _capture_voxel_inputs(model)
     g = torch.Generator().manual_seed(42)
     S, H, W = 2, 28, 28
     lat = torch.randn(1, cfg.C, S, H // 14, W // 14, generator=g)
@@ -220,6 +236,7 @@ def recon_tiny():
         "means": gs.means, "scales": gs.scales, "rotations": gs.rotations, "harmonics": gs.harmonics.half(),
         "opacities": gs.opacities, "c2w": ref.pred_context_pose["extrinsic"], "intrinsic": ref.pred_context_pose["intrinsic"],
         "scene_scale": ref.infos["scene_scale"].reshape(1),
+        **vox,
     })
 
 
@@ -234,6 +251,7 @@ def recon_mh():
     cfg = R.ReconCfg(**RECON_MH)
     sd = R.make_recon_weights(cfg, seed=43)
     model = build_reference_stitched(cfg, sd)
+    vox = _capture_voxel_inputs(model)
     g = torch.Generator().manual_seed(44)
     S, H, W = 3, 28, 42
     lat = torch.randn(1, cfg.C, S, H // 14, W // 14, generator=g)
@@ -275,6 +293,7 @@ def recon_mh():
         "means": gs.means, "scales": gs.scales, "rotations": gs.rotations, "opacities": gs.opacities,
         "c2w": ref.pred_context_pose["extrinsic"], "intrinsic": ref.pred_context_pose["intrinsic"],
         "scene_scale": ref.infos["scene_scale"].reshape(1),
+        **vox,
     })
 
 

@@ -236,13 +236,13 @@ def test_loaders_apply_every_checkpoint_piece(hip_lib, tmp_path):
 
 
 def test_bench_emits_the_contract_line(hip_lib):
-    """`bench.py` end to end on a shortened schedule (2 denoise steps, one scene, no CPU baseline leg): exactly one JSON line on stdout with
+    """`bench.py --full` end to end on a shortened schedule (2 denoise steps, one scene, no CPU baseline leg): exactly one JSON line on stdout with
     the driver's fields, the BASELINE metric / workload, the `roofline` object of the dominant kernel with a live-measured fraction, and a
     value consistent with ms_per_step."""
     import json, subprocess, sys
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "1", "--warmup", "0", "--denoise-steps", "2", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "1", "--warmup", "0", "--denoise-steps", "2", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=str(root))
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -258,6 +258,31 @@ def test_bench_emits_the_contract_line(hip_lib):
     assert rf["bound"] == "mfma" and rf["unit"] == "TFLOP/s" and rf["peak"] == 2500.0 and 0.2 < rf["frac"] < 0.8 and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-3
     assert rf["traffic"] is None or rf["traffic"] > 0
     assert "cpu_baseline" not in j      # (--no-cpu-baseline; the default run adds the object: profiles/rNN/bench_default_run.json)
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_scene(hip_lib, tmp_path):
+    """A plain `bench.py` (no --full) prints the headline fields and none of the --full objects; --dump-outputs writes what the last timed
+    scene returned (Gaussians, poses, depth, latents, clip) as float32 / float64 .npy files, at most 64 MB in all."""
+    import json, subprocess, sys
+    from pathlib import Path
+    import numpy as np
+    root = Path(__file__).resolve().parents[1]
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--steps", "2", "--warmup", "0", "--denoise-steps", "2", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=900, cwd=str(root))
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "config"):
+        assert k in j, k
+    assert j["steps"] == 2 and j["unit"] == "scenes/s" and j["dtype"] == "bf16" and abs(j["value"] * j["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    assert not {"roofline", "stage_roofline", "cpu_baseline"} & set(j) and "stage_ms_last_scene" not in j["config"]
+    got = {f.stem: np.load(f) for f in tmp_path.glob("*.npy")}
+    assert {"gaussians.means", "gaussians.harmonics", "pred_context_pose.extrinsic", "depth_dict.depth", "latents", "clip"} <= set(got)
+    assert sum(f.stat().st_size for f in tmp_path.glob("*.npy")) <= 64e6
+    for k, v in got.items():
+        assert v.dtype in (np.float32, np.float64) and np.isfinite(v).all(), k
+    assert got["latents"].shape == (1, 16, 4, 64, 64) and got["pred_context_pose.extrinsic"].shape == (1, 13, 4, 4)
 
 
 def test_graft_entry_build_then_smoke_in_one_process(hip_lib):

@@ -423,6 +423,38 @@ def test_bench_parses_the_rocm_smi_clock_and_power_sample():
     assert bench.parse_rocm_smi('{"card0": {"sclk clock speed:": "(95Mhz)", "Average Graphics Package Power (W)": "N/A"}}') is None
 
 
+def test_bench_dump_outputs_names_dtypes_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: every tensor / number of the returned structure under a dotted name; float32 (float64 for float64 and
+    integer arrays); arrays over their share of the byte budget replaced by a seeded sample that is the same on every run."""
+    import dataclasses
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    @dataclasses.dataclass
+    class G:
+        means: torch.Tensor
+        skip: object = None
+
+    big = torch.randn(4000, generator=torch.Generator().manual_seed(1))
+    out = dict(gaussians=G(big.to(torch.bfloat16)), pose=[torch.arange(6, dtype=torch.int64), torch.ones(3, dtype=torch.bool)], ratio=0.25)
+    arrays = {**bench.output_arrays(out), "clip": big}
+    assert list(arrays) == ["gaussians.means", "pose.0", "pose.1", "ratio", "clip"]
+    budget = 4 * 3000
+    for d in ("a", "b"):
+        bench.dump_outputs(arrays, tmp_path / d, budget=budget)
+    got = {f.stem: np.load(f) for f in sorted((tmp_path / "a").glob("*.npy"))}
+    assert set(got) == set(arrays)
+    assert got["pose.0"].dtype == np.float64 and got["pose.0"].tolist() == list(range(6))
+    assert got["pose.1"].dtype == np.float32 and got["ratio"].dtype == np.float64 and float(got["ratio"]) == 0.25
+    assert got["clip"].dtype == np.float32 and got["gaussians.means"].dtype == np.float32
+    assert sum(v.nbytes for v in got.values()) <= budget
+    assert 0 < got["clip"].size < big.numel() and np.isin(got["clip"], big.numpy()).all()
+    for k, v in got.items():
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy"))
+
+
 def test_committed_oracle_digests_match_the_current_oracle_sources():
     """tests/oracle_cache.py: every committed full-size digest carries the sha256 of the oracle sources that computed it; an edit of
     oracle/recon.py / oracle/wan_dit.py (or of the case definitions) without regenerating the digests fails HERE, on the CPU, not only

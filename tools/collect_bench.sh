@@ -8,9 +8,9 @@ O=$R/gpurun_out
 mkdir -p $O $R/profiles/r5
 bash tools/pmc_traffic.sh > /dev/null 2>&1; cp $O/pmc_traffic.json $O/prof_pmc_traffic.json; cp $O/pmc_traffic.json $R/profiles/r5/pmc_traffic.json; rm -rf $O/pmc_traffic_FETCH_SIZE $O/pmc_traffic_WRITE_SIZE
 bash tools/pmc_mfma.sh > /dev/null 2>&1; cp $O/pmc_mfma.json $O/prof_pmc_mfma.json; rm -rf $O/pmc_mfma
-python bench.py 2>/dev/null | tail -1 > $O/prof_bench_default_run.json
+python bench.py --full 2>/dev/null | tail -1 > $O/prof_bench_default_run.json
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/prof_bench_under_rocprof.json
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --full 2>/dev/null | tail -1 > $O/prof_bench_under_rocprof.json
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $O/prof_bench_kernel_stats.csv
 python $R/tools/trace_shapes.py /tmp/prof_stats 45 > $O/prof_bench_kernel_shapes.txt
 rm -rf /tmp/prof_stats

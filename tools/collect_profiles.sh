@@ -9,9 +9,9 @@ mkdir -p $O
 V3A_FULL_SIZE=${V3A_FULL_SIZE:-0} python -m pytest tests -q -m gpu -rP --durations=25 > $O/prof_gputest_stdout.log 2>&1   # incl. the production-size teacher-forced runs
 tail -3 $O/prof_gputest_stdout.log
 cp $O/parity.json $O/prof_parity.json
-python bench.py 2>/dev/null | tail -1 > $O/prof_bench_default_run.json
+python bench.py --full 2>/dev/null | tail -1 > $O/prof_bench_default_run.json
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline 2>/dev/null | tail -1 > $O/prof_bench_under_rocprof.json
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_stats -o b -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --full 2>/dev/null | tail -1 > $O/prof_bench_under_rocprof.json
 cp $(find /tmp/prof_stats -name "*kernel_stats.csv" | head -1) $O/prof_bench_kernel_stats.csv
 python $R/tools/trace_shapes.py /tmp/prof_stats 45 > $O/prof_bench_kernel_shapes.txt
 rm -rf /tmp/prof_stats
