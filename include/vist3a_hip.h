@@ -23,7 +23,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 21) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 22) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -478,6 +478,22 @@ typedef struct {
 } v3a_gs_rasterize_args;
 long v3a_gs_rasterize_workspace_bytes(long U, int C, int width, int height, long max_isect);
 int v3a_gs_rasterize(const v3a_gs_rasterize_args* a, void* stream);
+
+/* ---- Image-pair metrics of the novel-view-synthesis evaluation (calculate_metric.py; anysplat/src/evaluation/metrics.py:11-55):
+ * per pair, SSIM as skimage.metrics.structural_similarity(win_size=11, gaussian_weights=True, channel_axis=0, data_range=1.0)
+ * computes it, and the MSE of compute_psnr (PSNR = -10 log10(mse) on the host), both on uint8 / 255 in fp32 (PNG pixels read back
+ * with ToTensor).  One call = two launches; fp64 partials reduced in a fixed order (bit-identical run to run, no atomics).
+ * H, W >= 11 (skimage's minimum for win_size 11), 1 <= C <= 4. */
+typedef struct {
+  const uint8_t* a;         /* [N,H,W,C] uint8 (PNG byte order) */
+  const uint8_t* b;         /* [N,H,W,C] uint8 */
+  int N, H, W, C;
+  double* ssim;             /* out [N] */
+  double* mse;              /* out [N] */
+  void* workspace; long workspace_bytes;   /* v3a_image_metrics_workspace_bytes(N, H, W, C) */
+} v3a_image_metrics_args;
+long v3a_image_metrics_workspace_bytes(int N, int H, int W, int C);   /* V3A_ERR_SHAPE for a shape the metric rejects */
+int v3a_image_metrics(const v3a_image_metrics_args* a, void* stream);
 
 #ifdef __cplusplus
 }

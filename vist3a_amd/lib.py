@@ -184,6 +184,15 @@ class RowNormArgs(C.Structure):
     ]
 
 
+class ImageMetricsArgs(C.Structure):
+    _fields_ = [
+        ("a", C.c_void_p), ("b", C.c_void_p),
+        ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
+        ("ssim", C.c_void_p), ("mse", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/vist3a_hip.h declares must be listed here
 SYMBOLS = {
     "v3a_abi_version": (C.c_int, []),
@@ -236,10 +245,12 @@ SYMBOLS = {
     "v3a_gs_rasterize_workspace_bytes": (C.c_long, [C.c_long, C.c_int, C.c_int, C.c_int, C.c_long]),
     "v3a_gs_rasterize": (C.c_int, [C.POINTER(GsRasterizeArgs), C.c_void_p]),
     "v3a_softmax_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "v3a_image_metrics_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "v3a_image_metrics": (C.c_int, [C.POINTER(ImageMetricsArgs), C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 21   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 22   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

@@ -93,14 +93,20 @@ class AnySplatStitched(torch.nn.Module):
             self._engine = ReconEngine(self._cfg, self._sd, self._device)
         return self._engine
 
+    @staticmethod
+    def context_pose(out: dict, S: int, H: int, W: int) -> dict:
+        """engine poses -> pred_context_pose (b = 1): camera-to-world extrinsics [1,S,4,4], normalised intrinsics [1,S,3,3]
+        (anysplat_stitched.py:475-494)"""
+        ext, K = out["extrinsic_w2c"][None], out["intrinsic_px"][None]
+        pad = torch.tensor([0, 0, 0, 1.0], device=ext.device, dtype=ext.dtype).view(1, 1, 1, 4).repeat(1, S, 1, 1)
+        Kn = torch.stack([K[:, :, 0] / W, K[:, :, 1] / H, K[:, :, 2]], 2)
+        return dict(extrinsic=torch.cat([ext, pad], 2).inverse(), intrinsic=Kn)
+
     def package(self, out: dict, S: int, H: int, W: int, train: bool):
         """raw engine outputs -> EncoderOutput exactly as anysplat_stitched.py:448-525 assembles it (batch dim b = 1)."""
         g = out["gaussians"]
         gauss = Gaussians(**{k: v[None] for k, v in g.items()})
-        ext, K = out["extrinsic_w2c"][None], out["intrinsic_px"][None]
-        pad = torch.tensor([0, 0, 0, 1.0], device=ext.device, dtype=ext.dtype).view(1, 1, 1, 4).repeat(1, S, 1, 1)
-        Kn = torch.stack([K[:, :, 0] / W, K[:, :, 1] / H, K[:, :, 2]], 2)
-        pose = dict(extrinsic=torch.cat([ext, pad], 2).inverse(), intrinsic=Kn)
+        pose = self.context_pose(out, S, H, W)
         depth = out["depth"].view(1, S, H, W, 1)
         dconf = out["depth_conf"].view(1, S, H, W)
         U = g["means"].shape[0]

@@ -76,12 +76,13 @@ def load_vae(args, device):
     return WanVAEDecoder(cfg, sd, device=device)
 
 
-def load_stitching_model(args) -> StitchVAE3D:
+def load_stitching_model(args, vae=None) -> StitchVAE3D:
+    """vae: a prebuilt Wan VAE to use instead of load_vae(args) (the NVS evaluation's synthetic VAE that also encodes)"""
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
     if device.type != "cuda":
         raise RuntimeError("the MI355X path has no CPU fallback")
     ff = load_feedforward_model(args, device)
-    vae = load_vae(args, device)
+    vae = load_vae(args, device) if vae is None else vae
     model = StitchVAE3D(diffusion_vae=vae, feedforward_model=ff, device=device, stitching_layer_location=args.stitching_layer_location,
                         stitching_layer_config=args.stitching_layer_config, resolution=args.resolution,
                         stitching_layer_init_path=args.initialization_weight_path)

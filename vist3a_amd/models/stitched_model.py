@@ -71,6 +71,18 @@ class StitchVAE3D(torch.nn.Module):
         return self.forward_with_latent(latent, feedforward_image, train=train)
 
     @torch.no_grad()
+    def predict_poses(self, images, feedforward_image, generator: Optional[torch.Generator] = None) -> dict:
+        """Poses of the views only (the NVS evaluation's context + target pass, nvs_eval.py:97-108, keeps nothing else): the same
+        encode, posterior draw and stitching conv as `forward`, then the backbone and camera head (ReconEngine.forward_poses).
+        -> {"extrinsic" [1,S,4,4] camera-to-world, "intrinsic" [1,S,3,3] normalised}, bit-identical to `forward(...)
+        .pred_context_pose` on the same inputs and generator state."""
+        latent, _ = self.vae_encoder_forward(images, decode=False, generator=generator)
+        if latent.shape[0] != 1:
+            raise ValueError("predict_poses takes one scene (batch 1)")
+        out, (S, H, W) = self._scene(latent, feedforward_image, None, poses_only=True)
+        return self.stitched_3d_model.context_pose(out, S, H, W)
+
+    @torch.no_grad()
     def forward_with_latent(self, latent: torch.Tensor, feedforward_image: torch.Tensor, train: bool = False, image_cl: Optional[torch.Tensor] = None,
                             recon_group=None):
         """latent: de-normalised VAE latent [B,16,Tl,64,64]; feedforward_image [B,3,T,448,448] in [-1,1]
@@ -98,8 +110,12 @@ class StitchVAE3D(torch.nn.Module):
         out, (S, H, W) = self._scene(latent, feedforward_image, image_cl, grp)
         return self.stitched_3d_model.package(out, S, H, W, train)
 
-    def _scene(self, latent: torch.Tensor, feedforward_image: Optional[torch.Tensor], image_cl: Optional[torch.Tensor], grp=None):
-        """one scene: T-upsample -> stitching conv into the token workspace -> reconstruction engine; -> (raw engine outputs, (S, H, W))"""
+    def _scene(self, latent: torch.Tensor, feedforward_image: Optional[torch.Tensor], image_cl: Optional[torch.Tensor], grp=None,
+               poses_only: bool = False):
+        """one scene: T-upsample -> stitching conv into the token workspace -> reconstruction engine; -> (raw engine outputs, (S, H, W)).
+        poses_only: stop after the camera head (ReconEngine.forward_poses; this GPU alone)."""
+        if poses_only and grp is not None and grp.world > 1:
+            raise NotImplementedError("the poses-only pass runs on one GPU")
         st = self.stitching_layer
         eng = self.stitched_3d_model.engine()
         lat_cl = ops.latent_upsample_t_cl(latent[0].to(device=self.device, dtype=torch.float32).contiguous())
@@ -133,4 +149,6 @@ class StitchVAE3D(torch.nn.Module):
             out = eng.forward_sharded(S, H, W, x, img01.contiguous(), grp, timings=times)
             self.recon_shard_times = times      # (last scene, this rank)
             return out, (S, H, W)
+        if poses_only:
+            return eng.forward_poses(S, H, W), (S, H, W)
         return eng.forward_tokens_filled(S, H, W, img01.contiguous()), (S, H, W)

@@ -1043,3 +1043,26 @@ def gs_rasterize(proj: dict, opacities: torch.Tensor, width: int, height: int, *
     if return_order:
         out["tile_offsets"], out["flatten_ids"] = offs, ids[: n_host.value]
     return out
+
+
+def image_metrics(a_u8: torch.Tensor, b_u8: torch.Tensor):
+    """SSIM and MSE of N uint8 image pairs [N,H,W,C] (PNG byte order; pixels scored as u8 / 255) in one call
+    (csrc/image_metrics.hip).  -> (ssim [N] f64, mse [N] f64) on the device; PSNR = -10 log10(mse) is the caller's."""
+    for name, t in (("a_u8", a_u8), ("b_u8", b_u8)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+        if t.dtype != torch.uint8 or t.dim() != 4 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous uint8 [N,H,W,C] tensor, got {t.dtype} {tuple(t.shape)}")
+    if a_u8.shape != b_u8.shape:
+        raise ValueError(f"image shapes differ: {tuple(a_u8.shape)} vs {tuple(b_u8.shape)}")
+    N, H, W, Cc = a_u8.shape
+    lib = L.load()
+    need = lib.v3a_image_metrics_workspace_bytes(N, H, W, Cc)
+    if need < 0:
+        L.check(int(need), f"v3a_image_metrics_workspace_bytes (shape {tuple(a_u8.shape)})")
+    ws = torch.empty(max(int(need), 1), device=a_u8.device, dtype=torch.uint8)
+    ssim = torch.empty(N, device=a_u8.device, dtype=torch.float64)
+    mse = torch.empty(N, device=a_u8.device, dtype=torch.float64)
+    args = L.ImageMetricsArgs(_ptr(a_u8), _ptr(b_u8), N, H, W, Cc, _ptr(ssim), _ptr(mse), _ptr(ws), ws.numel())
+    L.check(lib.v3a_image_metrics(C.byref(args), _stream()), "v3a_image_metrics")
+    return ssim, mse

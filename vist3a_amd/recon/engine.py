@@ -495,6 +495,17 @@ class ReconEngine:
         depth, dconf, pts, raw_gs, ext, K = self.heads(g, S, H, W, img_cl, poses[-1])
         return self._tail(S, H, W, poses, depth, dconf, pts, raw_gs, ext, K)
 
+    @torch.no_grad()
+    def forward_poses(self, S: int, H: int, W: int) -> dict:
+        """Poses-only pass over the filled token workspace: backbone + camera head, the cut right after `camera` in
+        forward_tokens_filled.  The NVS evaluation's second forward (nvs_eval.py:97-108) keeps only its poses; the DPT heads,
+        voxelization and adapter are not run.  Same kernels in the same order as the full forward: bit-identical poses."""
+        g = self._geometry(S, H, W)
+        self.backbone(g, S)
+        poses = self.camera(g, S)
+        ext, K = pose_encoding_to_extri_intri(poses[-1], (H, W))
+        return dict(pred_pose_enc_list=poses, extrinsic_w2c=ext, intrinsic_px=K)
+
     def _tail(self, S, H, W, poses, depth, dconf, pts, raw_gs, ext, K) -> dict:
         """per-pixel maps of all S views -> confidence mask / voxel fusion / Gaussian adapter (anysplat_stitched.py:381-453)"""
         cfg = self.cfg
