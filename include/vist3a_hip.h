@@ -23,7 +23,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 22) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 23) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -494,6 +494,25 @@ typedef struct {
 } v3a_image_metrics_args;
 long v3a_image_metrics_workspace_bytes(int N, int H, int W, int C);   /* V3A_ERR_SHAPE for a shape the metric rejects */
 int v3a_image_metrics(const v3a_image_metrics_args* a, void* stream);
+
+/* ---- LPIPS(VGG) of the novel-view-synthesis evaluation (calculate_metric.py; anysplat/src/evaluation/metrics.py:22-34, lpips 0.1
+ * `LPIPS(net="vgg")` with normalize=True).  The 13 VGG-16 convolutions are v3a_conv_split (act RELU, pair output); these are the passes
+ * around them (csrc/lpips.hip).  A pair tensor is two bf16 planes (hi, lo) of the same shape, channels-last.
+ *   v3a_lpips_input   pred, gt: uint8 [N,H,W,3] (f32_nchw = 0) or f32 [N,3,H,W] in [0,1] (f32_nchw = 1) -> y planes [2N][H][W][CinP]
+ *                     (frames [0,N) = pred, [N,2N) = gt; CinP 8 or 16, channels 3.. zero): fp32 x = u / 255, 2 x - 1, (x - shift) / scale
+ *                     (lpips ScalingLayer), each step rounded as torch rounds it, then split (hi, lo).  2N <= 65535.
+ *   v3a_lpips_pool    nn.MaxPool2d(2, 2), floor mode, on pair planes [F][H][W][C] -> [F][H/2][W/2][C] (C % 8 == 0): (hi, lo) compared
+ *                     lexicographically, the winner copied verbatim.
+ *   v3a_lpips_head    one tapped layer, planes [2N][h][w][C] (C = 8 * 2^k <= 512), lin weight f32 [C]: per pixel f = hi + lo,
+ *                     f^ = f / (sqrt(sum_c f^2) + 1e-10), d = sum_c w[c] (f^_pred - f^_gt)^2 in fp64; out[n] = mean of d over h x w
+ *                     (accumulate != 0: added to out[n]).  Two launches, fp64 partials reduced in a fixed order that depends on
+ *                     (h, w, C) only: bit-identical run to run and for any N.  workspace: v3a_lpips_head_workspace_bytes(N, h, w, C)
+ *                     (V3A_ERR_SHAPE for a shape the head rejects). */
+int v3a_lpips_input(const void* pred, const void* gt, int f32_nchw, int N, int H, int W, int CinP, void* y_hi, void* y_lo, void* stream);
+int v3a_lpips_pool(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, int F, int H, int W, int C, void* stream);
+long v3a_lpips_head_workspace_bytes(int N, int h, int w, int C);
+int v3a_lpips_head(const void* x_hi, const void* x_lo, const float* weight, int N, int h, int w, int C, double* out, int accumulate,
+                   void* workspace, long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

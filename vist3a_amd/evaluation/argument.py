@@ -51,3 +51,26 @@ def stitching_nvs_evaluation_argument() -> argparse.ArgumentParser:
     g.add_argument("--max_sequences", type=int, default=None, help="evaluate at most this many sequences")
     g.add_argument("--save_suffix", type=str, default=None, help="calculate_metric.py: write overall-metric-<suffix>.csv")
     return p
+
+
+class _MetricParser(argparse.ArgumentParser):
+    """rejects one LPIPS weight file without the other"""
+
+    def parse_known_args(self, args=None, namespace=None):
+        ns, rest = super().parse_known_args(args, namespace)
+        if (ns.lpips_vgg_weights is None) != (ns.lpips_lin_weights is None):
+            self.error("--lpips_vgg_weights and --lpips_lin_weights go together: give both or neither")
+        return ns, rest
+
+
+def calculate_metric_argument() -> argparse.ArgumentParser:
+    """calculate_metric.py's command line: stitching_nvs_evaluation_argument() plus the two LPIPS weight files (not in the reference,
+    whose lpips package finds its own).  Without them LPIPS is not computed."""
+    p = _MetricParser(description="Stitching NVS evaluation argument", formatter_class=argparse.ArgumentDefaultsHelpFormatter,
+                      parents=[stitching_nvs_evaluation_argument()], add_help=False)
+    g = p.add_argument_group("LPIPS (not in the reference)")
+    g.add_argument("--lpips_vgg_weights", type=str, default=None, metavar="PATH",
+                   help="torchvision's VGG-16 state dict (vgg16-397923af.pth, or a .safetensors of it)")
+    g.add_argument("--lpips_lin_weights", type=str, default=None, metavar="PATH",
+                   help="the lpips package's weights/v0.1/vgg.pth (lin0..lin4)")
+    return p

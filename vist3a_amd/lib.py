@@ -247,10 +247,14 @@ SYMBOLS = {
     "v3a_softmax_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "v3a_image_metrics_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "v3a_image_metrics": (C.c_int, [C.POINTER(ImageMetricsArgs), C.c_void_p]),
+    "v3a_lpips_input": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
+    "v3a_lpips_pool": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "v3a_lpips_head_workspace_bytes": (C.c_long, [C.c_int] * 4),
+    "v3a_lpips_head": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 22   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 23   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

@@ -1066,3 +1066,55 @@ def image_metrics(a_u8: torch.Tensor, b_u8: torch.Tensor):
     args = L.ImageMetricsArgs(_ptr(a_u8), _ptr(b_u8), N, H, W, Cc, _ptr(ssim), _ptr(mse), _ptr(ws), ws.numel())
     L.check(lib.v3a_image_metrics(C.byref(args), _stream()), "v3a_image_metrics")
     return ssim, mse
+
+
+# ------------------------------------------------------------------------------------------------ LPIPS(VGG) passes (csrc/lpips.hip)
+def lpips_input(pred: torch.Tensor, gt: torch.Tensor, cin_pad: int = 16) -> torch.Tensor:
+    """N pred and N gt images -> ONE pair [2, 2N, H, W, cin_pad] (frames [0,N) = pred, [N,2N) = gt), lpips' input transform
+    (ToTensor's u8 / 255 where uint8, 2 x - 1, ScalingLayer) in fp32.  pred / gt: uint8 [N,H,W,3] (PNG bytes) or f32 [N,3,H,W] in [0,1]."""
+    for name, t in (("pred", pred), ("gt", gt)):
+        if not t.is_cuda:
+            raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+        if t.dtype not in (torch.uint8, f32) or t.dim() != 4 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous uint8 [N,H,W,3] or f32 [N,3,H,W] tensor, got {t.dtype} {tuple(t.shape)}")
+    if pred.shape != gt.shape or pred.dtype != gt.dtype:
+        raise ValueError(f"pred and gt differ: {pred.dtype} {tuple(pred.shape)} vs {gt.dtype} {tuple(gt.shape)}")
+    nchw = pred.dtype == f32
+    N, H, W = (pred.shape[0], pred.shape[2], pred.shape[3]) if nchw else pred.shape[:3]
+    if (pred.shape[1] if nchw else pred.shape[3]) != 3:
+        raise ValueError(f"LPIPS takes 3-channel images, got shape {tuple(pred.shape)}")
+    out = torch.empty((2, 2 * N, H, W, cin_pad), device=pred.device, dtype=bf16)
+    L.check(L.load().v3a_lpips_input(_ptr(pred), _ptr(gt), int(nchw), N, H, W, cin_pad, _ptr(out[0]), _ptr(out[1]), _stream()),
+            "v3a_lpips_input")
+    return out
+
+
+def lpips_pool(x: torch.Tensor) -> torch.Tensor:
+    """nn.MaxPool2d(2, 2) (floor mode) of a pair [2, F, H, W, C]: exact, the winning (hi, lo) is copied"""
+    if x.dim() != 5 or x.shape[0] != 2 or not x.is_contiguous() or x.dtype != bf16 or not x.is_cuda:
+        raise ValueError("x must be a contiguous device bf16 pair [2,F,H,W,C]")
+    _, F, H, W, Cc = x.shape
+    out = torch.empty((2, F, H // 2, W // 2, Cc), device=x.device, dtype=bf16)
+    L.check(L.load().v3a_lpips_pool(_ptr(x[0]), _ptr(x[1]), _ptr(out[0]), _ptr(out[1]), F, H, W, Cc, _stream()), "v3a_lpips_pool")
+    return out
+
+
+def lpips_head(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor, accumulate: bool = False) -> torch.Tensor:
+    """one tapped layer of LPIPS: x pair [2, 2N, h, w, C] (frames [0,N) pred, [N,2N) gt), weight f32 [C] (lin{l}.model.1.weight) ->
+    out f64 [N] = the spatial mean of sum_c w (f^_pred - f^_gt)^2, or out += it with accumulate"""
+    if x.dim() != 5 or x.shape[0] != 2 or x.shape[1] % 2 or not x.is_contiguous() or x.dtype != bf16 or not x.is_cuda:
+        raise ValueError("x must be a contiguous device bf16 pair [2,2N,h,w,C]")
+    _, F, h, w, Cc = x.shape
+    N = F // 2
+    if weight.dtype != f32 or not weight.is_contiguous() or weight.numel() != Cc or weight.device != x.device:
+        raise ValueError(f"weight must be a contiguous f32 [{Cc}] tensor on {x.device}")
+    if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != N or out.device != x.device:
+        raise ValueError(f"out must be a contiguous f64 [{N}] tensor on {x.device}")
+    lib = L.load()
+    need = lib.v3a_lpips_head_workspace_bytes(N, h, w, Cc)
+    if need < 0:
+        L.check(int(need), f"v3a_lpips_head_workspace_bytes (shape {tuple(x.shape)})")
+    ws = torch.empty(max(int(need), 1), device=x.device, dtype=torch.uint8)
+    L.check(lib.v3a_lpips_head(_ptr(x[0]), _ptr(x[1]), _ptr(weight), N, h, w, Cc, _ptr(out), int(accumulate), _ptr(ws), ws.numel(),
+                               _stream()), "v3a_lpips_head")
+    return out
