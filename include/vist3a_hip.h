@@ -23,7 +23,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 23) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 24) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -478,6 +478,64 @@ typedef struct {
 } v3a_gs_rasterize_args;
 long v3a_gs_rasterize_workspace_bytes(long U, int C, int width, int height, long max_isect);
 int v3a_gs_rasterize(const v3a_gs_rasterize_args* a, void* stream);
+
+/* ---- Backward of the two stages (csrc/raster_bwd.hip): what gsplat's rasterize_to_pixels_bwd, fully_fused_projection_bwd and
+ * spherical_harmonics_bwd hand torch.autograd for the call above.  fp32; no float atomics: every sum has a fixed order, so results
+ * are bit-identical run to run.  The radius, culling, binning and early-stop decisions of the forward are constants, as in gsplat.
+ * NOT computed: gradients to viewmat / campos / K (gsplat's optional pose gradients; the reference leaves cam_rot_delta /
+ * cam_trans_delta unused), cov_ignore=True (quaternion / scale input), packed mode, antialiased mode.
+ *
+ * Stage 2 backward.  Takes the forward's projected arrays, its composite order (tile_offsets_out / flatten_ids_out and *n_isect of
+ * v3a_gs_rasterize) and dL/d(out_color, out_depth, out_alpha); returns the gradient of every camera-Gaussian entry.  Each pixel
+ * re-walks its tile list front to back with the forward's arithmetic (same __expf), so it stops where the forward stopped, skips
+ * what it skipped (sigma < 0, alpha < 1/255), passes no gradient through an alpha held at the 0.999 cap or a colour clipped by
+ * clamp_rgb, and needs neither out_color nor out_alpha.  Workspace: two counters per entry + one 48-byte row per intersection. */
+typedef struct {
+  const int* radii; const float* means2d; const float* conics; const float* colors;   /* [C,U], [C,U,2], [C,U,3], [C,U,4] */
+  const float* opacities;   /* [U] */
+  const float* background;  /* [3] or NULL */
+  long U;
+  int C;
+  int width, height;
+  int clamp_rgb;
+  const unsigned int* tile_offsets;  /* [C*ntiles+1] */
+  const unsigned int* flatten_ids;   /* [n_isect] entry ids c*U+g in composite order (may be NULL when n_isect == 0) */
+  long n_isect;
+  const float* d_color;     /* [C,H,W,3] */
+  const float* d_depth;     /* [C,H,W] */
+  const float* d_alpha;     /* [C,H,W] */
+  float* d_means2d;         /* out [C,U,2] */
+  float* d_conics;          /* out [C,U,3] */
+  float* d_colors;          /* out [C,U,4] rgb + the depth channel */
+  float* d_opacity_partial; /* out [C,U]: this camera's share of dL/d opacities[g] */
+  void* workspace; long workspace_bytes;   /* v3a_gs_rasterize_backward_workspace_bytes(U, C, width, height, n_isect); too small: -4 */
+} v3a_gs_rasterize_backward_args;
+long v3a_gs_rasterize_backward_workspace_bytes(long U, int C, int width, int height, long max_isect);
+int v3a_gs_rasterize_backward(const v3a_gs_rasterize_backward_args* a, void* stream);
+
+/* Stage 1 backward: the entry gradients above -> dL/d(means, covars, sh, opacities), summed over the C cameras in index order.
+ * Through the conic (inverse of J Cc J^T + eps2d I), the clamped tx / ty (gradient of min / max as torch takes it), the pixel
+ * mean, the depth channel (colors[...,3] = z), the world -> camera rotation of mean and covariance, and the SH colour with its
+ * clamp_min(c + 0.5, 0) mask: to the coefficients and, through the normalised view direction, to the means.  Entries with
+ * radii == 0 contribute exactly zero.  d_covars follows the forward's "the upper triangle is used": lower-triangle entries are
+ * zero, an upper off-diagonal entry carries both symmetric positions.  d_sh has the layout of sh: all sh_k columns are written,
+ * bands >= (sh_degree+1)^2 are zero. */
+typedef struct {
+  const float* means; const float* covars; const float* sh;
+  int sh_layout, sh_k, sh_degree;
+  const float* viewmat; const float* campos; const float* K;
+  long U;
+  int C;
+  int width, height;
+  float eps2d;
+  const int* radii;                /* [C,U] of the forward */
+  const float* d_means2d; const float* d_conics; const float* d_colors; const float* d_opacity_partial;
+  float* d_means;           /* out [U,3] */
+  float* d_covars;          /* out [U,3,3] */
+  float* d_sh;              /* out, shape and layout of sh */
+  float* d_opacities;       /* out [U] */
+} v3a_gs_project_backward_args;
+int v3a_gs_project_backward(const v3a_gs_project_backward_args* a, void* stream);
 
 /* ---- Image-pair metrics of the novel-view-synthesis evaluation (calculate_metric.py; anysplat/src/evaluation/metrics.py:11-55):
  * per pair, SSIM as skimage.metrics.structural_similarity(win_size=11, gaussian_weights=True, channel_axis=0, data_range=1.0)

@@ -1,0 +1,582 @@
+// Backward of the 3D-Gaussian rasteriser (raster.hip) for gfx950, fp32: what gsplat's rasterize_to_pixels_bwd +
+// fully_fused_projection_bwd + spherical_harmonics_bwd give torch.autograd, for the same call the forward replaces
+// (RGB+D, classic, packed=False, explicit world covariances).  Gradients reach means, covars, sh and opacities; cameras are constants.
+//
+//   v3a_gs_rasterize_backward   count + rocPRIM scan (the forward's, re-run: each camera-Gaussian entry's first row slot) ->
+//                               gs_blend_bwd_kernel, one 256-lane workgroup per 16x16 tile of every camera: walks the tile's
+//                               list front to back exactly as the forward does to find every pixel's final T and stop index,
+//                               then back to front; the ten per-pixel terms of a Gaussian are summed over the wave with DPP,
+//                               over the four waves through LDS, and the (Gaussian, tile) row leaves the workgroup ONCE, with
+//                               plain stores, to slot  first(entry) + tile's position inside the entry's tile rectangle ->
+//                               gs_rowsum_kernel adds an entry's rows in slot order.
+//   v3a_gs_project_backward     one wave per 64 Gaussians looping over the cameras in index order (as the forward): conic ->
+//                               2D covariance -> J, camera covariance -> world covariance; mean through J, the pixel mean,
+//                               the depth channel and the SH view direction; SH coefficients.
+// No atomics on floats anywhere: every sum has a fixed order, results are bit-identical run to run.
+#include <rocprim/device/device_scan.hpp>
+
+#include "common.h"
+#include "gs_raster.h"
+#include "../../include/vist3a_hip.h"
+
+namespace {
+
+using namespace gs;
+
+constexpr int ROWF = 12;  // floats per row: d_means2d (2) d_conics (3) d_colors (4) d_opacity (1), padded to three 16-byte stores
+constexpr int BB = 128;   // Gaussians per backward round (4 waves x BB x 48 B of LDS partials)
+
+__host__ __device__ __forceinline__ float fast_exp(float x) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __expf(x);  // the forward's: both passes must see the same alpha
+#else
+  return expf(x);
+#endif
+}
+__host__ __device__ __forceinline__ float fast_rcp(float x) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __builtin_amdgcn_rcpf(x);
+#else
+  return 1.f / x;
+#endif
+}
+
+// One pixel x one Gaussian of the back-to-front walk.  In: T = transmittance BEHIND this Gaussian (updated to the one in front),
+// S[4] = colour accumulated behind it (updated), g[4] = dL/d(rgb, depth) of the pixel, gT = dL/dT_final, Tfin.  Out: the ten terms.
+__host__ __device__ __forceinline__ void blend_bwd_pair(float dx, float dy, float ca, float cb, float cc, float opac, float ex, float alpha,
+                                                        const f32x4& col, const float* g, float gT, float Tfin, float& T, float* S,
+                                                        float* v) {
+  const float ra = fast_rcp(1.f - alpha);
+  T *= ra;
+  const float vis = alpha * T;
+  float va = -Tfin * ra * gT;
+#pragma unroll
+  for (int ch = 0; ch < 4; ++ch) {
+    v[5 + ch] = vis * g[ch];
+    va += (col[ch] * T - S[ch] * ra) * g[ch];
+    S[ch] += col[ch] * vis;
+  }
+  const float raw = opac * ex;
+  if (raw <= 0.999f) {  // clamp_max passes the gradient only below the cap
+    const float vs = -raw * va;
+    v[0] = vs * (ca * dx + cb * dy);
+    v[1] = vs * (cb * dx + cc * dy);
+    v[2] = 0.5f * vs * dx * dx;
+    v[3] = vs * dx * dy;
+    v[4] = 0.5f * vs * dy * dy;
+    v[9] = ex * va;
+  } else {
+    v[0] = v[1] = v[2] = v[3] = v[4] = v[9] = 0.f;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------- row slots
+struct CountP {
+  const int* radii; const float* means2d;
+  long CU;
+  int tw, th;
+  unsigned int* counts;
+};
+
+__global__ __launch_bounds__(256) void gs_bwd_count_kernel(CountP p) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= p.CU) return;
+  unsigned int n = 0;
+  const int r = p.radii[e];
+  if (r > 0) {
+    int x0, x1, y0, y1;
+    tile_bounds(p.means2d[2 * e], p.means2d[2 * e + 1], r, p.tw, p.th, x0, x1, y0, y1);
+    n = (unsigned int)((x1 - x0) * (y1 - y0));
+  }
+  p.counts[e] = n;
+}
+
+// ---------------------------------------------------------------------------------------------- blend backward
+struct BlendBwdP {
+  const int* radii; const float* means2d; const float* conics; const float* colors; const float* opac;
+  const unsigned int* offs; const unsigned int* ids; const unsigned int* counts; const unsigned int* incl;
+  const float* bg; const float* d_color; const float* d_depth; const float* d_alpha;
+  float* rows;
+  unsigned int n_isect, CU;
+  int U, W, H, tw, th, ntiles, clamp_rgb;
+};
+
+// wave_sum of common.h without the final broadcast: lane 63 holds the sum (the only lane that stores it)
+__device__ __forceinline__ float wave_sum_lane63(float v) {
+  v += dpp_f32<0xB1>(0.f, v);
+  v += dpp_f32<0x4E>(0.f, v);
+  v += dpp_f32<0x141>(0.f, v);
+  v += dpp_f32<0x140>(0.f, v);
+  v += dpp_f32<0x142, 0xA>(0.f, v);
+  v += dpp_f32<0x143, 0xC>(0.f, v);
+  return v;
+}
+
+// row slot of entry `id` in tile (tx, ty): the entry's rows are its tile rectangle in row-major order; ~0u = not a valid pair
+__device__ __forceinline__ unsigned int row_slot(const BlendBwdP& p, unsigned int id, int tx, int ty) {
+  if (id >= p.CU) return ~0u;
+  const int r = p.radii[id];
+  if (r <= 0) return ~0u;
+  int x0, x1, y0, y1;
+  tile_bounds(p.means2d[2L * id], p.means2d[2L * id + 1], r, p.tw, p.th, x0, x1, y0, y1);
+  if (tx < x0 || tx >= x1 || ty < y0 || ty >= y1) return ~0u;
+  const unsigned int slot = p.incl[id] - p.counts[id] + (unsigned int)((ty - y0) * (x1 - x0) + (tx - x0));
+  return slot < p.n_isect ? slot : ~0u;
+}
+
+// stage one Gaussian of a tile list into LDS (the forward's three 16-byte records); an id outside the call reads as transparent
+__device__ __forceinline__ void stage_gaussian(const BlendBwdP& p, unsigned int id, int cam, f32x4* dst) {
+  f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = a, col = a;
+  const unsigned int gi = id - (unsigned int)cam * (unsigned int)p.U;
+  if (id < p.CU && gi < (unsigned int)p.U) {
+    a = f32x4{p.means2d[2L * id], p.means2d[2L * id + 1], p.opac[gi], 0.f};
+    c = f32x4{p.conics[3L * id], p.conics[3L * id + 1], p.conics[3L * id + 2], 0.f};
+    col = *(const f32x4*)(p.colors + 4L * id);
+  }
+  dst[0] = a; dst[1] = c; dst[2] = col;
+}
+
+__global__ __launch_bounds__(256) void gs_blend_bwd_kernel(BlendBwdP p) {
+  __shared__ f32x4 s_g[256 * 3];        // {x, y, opacity, -} {conic a, b, c, -} {r, g, b, depth}
+  __shared__ f32x4 s_part[4][BB][3];    // per wave, per Gaussian of the round: the ten reduced terms
+  __shared__ unsigned int s_slot[BB];
+  __shared__ unsigned int s_stop;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int cam = blockIdx.x / p.ntiles, tile = blockIdx.x - cam * p.ntiles;
+  const int tx = tile % p.tw, ty = tile / p.tw;
+  const int px_i = tx * TILE + (tid & 15), py_i = ty * TILE + (tid >> 4);
+  const bool inside = px_i < p.W && py_i < p.H;
+  const float px = (float)px_i + 0.5f, py = (float)py_i + 0.5f;
+  const unsigned int e = min(p.offs[blockIdx.x + 1], p.n_isect), s = min(p.offs[blockIdx.x], e);
+  if (tid == 0) s_stop = s;
+
+  // ---- front to back, the forward's loop: final T, pre-clamp colour, and the list index this pixel stopped at
+  float T = 1.f, r = 0.f, g = 0.f, b = 0.f;
+  unsigned int stop = inside ? e : s;
+  bool done = !inside;
+  for (unsigned int base = s; base < e; base += 256) {
+    if (__syncthreads_and(done)) break;  // also the barrier that protects s_g from the previous round's readers
+    const unsigned int n = min(256u, e - base);
+    if ((unsigned int)tid < n) stage_gaussian(p, p.ids[base + tid], cam, s_g + 3 * tid);
+    __syncthreads();
+    if (!done) {
+      for (unsigned int k = 0; k < n; ++k) {
+        const f32x4 a = s_g[3 * k], c = s_g[3 * k + 1];
+        const float dx = a[0] - px, dy = a[1] - py;
+        const float sigma = 0.5f * (c[0] * dx * dx + c[2] * dy * dy) + c[1] * dx * dy;
+        const float alpha = fminf(0.999f, a[2] * fast_exp(-sigma));
+        if (sigma < 0.f || alpha < 1.f / 255.f) continue;
+        const float nT = T * (1.f - alpha);
+        if (nT <= 1e-4f) { done = true; stop = base + k; break; }
+        const float vis = alpha * T;
+        const f32x4 col = s_g[3 * k + 2];
+        r += col[0] * vis; g += col[1] * vis; b += col[2] * vis;
+        T = nT;
+      }
+    }
+  }
+  // incoming gradients of this pixel; the clamp passes them where the un-clamped value lies in [0, 1], as torch.clamp does
+  float gr[4] = {0.f, 0.f, 0.f, 0.f}, gT = 0.f;
+  const float Tfin = T;
+  if (inside) {
+    const long pix = ((long)cam * p.H + py_i) * p.W + px_i;
+    if (p.bg) { r += T * p.bg[0]; g += T * p.bg[1]; b += T * p.bg[2]; }
+    gr[0] = p.d_color[3 * pix]; gr[1] = p.d_color[3 * pix + 1]; gr[2] = p.d_color[3 * pix + 2];
+    if (p.clamp_rgb) {
+      if (!(r >= 0.f && r <= 1.f)) gr[0] = 0.f;
+      if (!(g >= 0.f && g <= 1.f)) gr[1] = 0.f;
+      if (!(b >= 0.f && b <= 1.f)) gr[2] = 0.f;
+    }
+    gr[3] = p.d_depth[pix];
+    gT = -p.d_alpha[pix];
+    if (p.bg) gT += gr[0] * p.bg[0] + gr[1] * p.bg[1] + gr[2] * p.bg[2];
+  }
+  __syncthreads();
+  atomicMax(&s_stop, stop);  // integer maximum in LDS: order-independent
+  __syncthreads();
+  const unsigned int wg_stop = s_stop;  // no pixel of the tile went past this list index
+
+  // ---- back to front
+  float S[4] = {0.f, 0.f, 0.f, 0.f};
+  const int nround = (int)((wg_stop - s + BB - 1) / BB);
+  for (int rd = nround - 1; rd >= 0; --rd) {
+    const unsigned int base = s + (unsigned int)rd * BB;
+    const int n = (int)min((unsigned int)BB, wg_stop - base);
+    __syncthreads();  // the previous round's readers of s_g / s_part / s_slot
+    if (tid < n) {
+      const unsigned int id = p.ids[base + tid];
+      stage_gaussian(p, id, cam, s_g + 3 * tid);
+      s_slot[tid] = row_slot(p, id, tx, ty);
+    }
+    __syncthreads();
+    for (int k = n - 1; k >= 0; --k) {
+      const f32x4 a = s_g[3 * k], c = s_g[3 * k + 1];
+      const float dx = a[0] - px, dy = a[1] - py;
+      const float sigma = 0.5f * (c[0] * dx * dx + c[2] * dy * dy) + c[1] * dx * dy;
+      const float ex = fast_exp(-sigma);
+      const float alpha = fminf(0.999f, a[2] * ex);
+      const bool valid = (base + (unsigned int)k < stop) && !(sigma < 0.f || alpha < 1.f / 255.f);
+      f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0, o2 = o0;
+      if (__any(valid)) {  // wave-uniform: a wave is four pixel rows, most Gaussians touch few of them
+        float v[10];
+#pragma unroll
+        for (int i = 0; i < 10; ++i) v[i] = 0.f;
+        if (valid) blend_bwd_pair(dx, dy, c[0], c[1], c[2], a[2], ex, alpha, s_g[3 * k + 2], gr, gT, Tfin, T, S, v);
+#pragma unroll
+        for (int i = 0; i < 10; ++i) v[i] = wave_sum_lane63(v[i]);
+        o0 = f32x4{v[0], v[1], v[2], v[3]}; o1 = f32x4{v[4], v[5], v[6], v[7]}; o2 = f32x4{v[8], v[9], 0.f, 0.f};
+      }
+      if (lane == 63) { s_part[wave][k][0] = o0; s_part[wave][k][1] = o1; s_part[wave][k][2] = o2; }
+    }
+    __syncthreads();
+    if (tid < n) {
+      const unsigned int slot = s_slot[tid];
+      if (slot != ~0u) {
+        f32x4 q[3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) q[j] = ((s_part[0][tid][j] + s_part[1][tid][j]) + s_part[2][tid][j]) + s_part[3][tid][j];
+        f32x4* dst = (f32x4*)(p.rows + (size_t)slot * ROWF);
+        dst[0] = q[0]; dst[1] = q[1]; dst[2] = q[2];
+      }
+    }
+  }
+  // pairs behind the last stop were never composited: their rows are zero (every row slot is written exactly once, no memset)
+  for (unsigned int i = wg_stop + tid; i < e; i += 256) {
+    const unsigned int slot = row_slot(p, p.ids[i], tx, ty);
+    if (slot != ~0u) {
+      f32x4* dst = (f32x4*)(p.rows + (size_t)slot * ROWF);
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+      dst[0] = z; dst[1] = z; dst[2] = z;
+    }
+  }
+}
+
+struct RowSumP {
+  const unsigned int* counts; const unsigned int* incl; const float* rows;
+  long CU;
+  unsigned int n_isect;
+  float* d_means2d; float* d_conics; float* d_colors; float* d_opac;
+};
+
+// one lane per camera-Gaussian entry: its rows in slot order (tile rectangle, row-major)
+__global__ __launch_bounds__(256) void gs_rowsum_kernel(RowSumP p) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= p.CU) return;
+  const unsigned int cnt = p.counts[e], first = p.incl[e] - cnt;
+  f32x4 q0 = {0.f, 0.f, 0.f, 0.f}, q1 = q0, q2 = q0;
+  if (first <= p.n_isect && cnt <= p.n_isect - first) {
+    const f32x4* src = (const f32x4*)(p.rows + (size_t)first * ROWF);
+    for (unsigned int i = 0; i < cnt; ++i) { q0 += src[3 * i]; q1 += src[3 * i + 1]; q2 += src[3 * i + 2]; }
+  }
+  p.d_means2d[2 * e] = q0[0]; p.d_means2d[2 * e + 1] = q0[1];
+  p.d_conics[3 * e] = q0[2]; p.d_conics[3 * e + 1] = q0[3]; p.d_conics[3 * e + 2] = q1[0];
+  *(f32x4*)(p.d_colors + 4 * e) = f32x4{q1[1], q1[2], q1[3], q2[0]};
+  p.d_opac[e] = q2[1];
+}
+
+struct BLayout { size_t counts, incl, rows, tmp, tmp_bytes, total; };
+
+BLayout blayout(long CU, long cap) {
+  BLayout l{};
+  size_t off = 0;
+  auto take = [&](size_t b) { size_t o = off; off += al256(b); return o; };
+  l.counts = take(4 * (size_t)CU); l.incl = take(4 * (size_t)CU);
+  l.rows = take(sizeof(float) * ROWF * (size_t)cap);
+  size_t t = 0;
+  (void)rocprim::inclusive_scan(nullptr, t, (unsigned int*)nullptr, (unsigned int*)nullptr, (size_t)CU, rocprim::plus<unsigned int>());
+  l.tmp_bytes = t;
+  l.tmp = take(t);
+  l.total = off;
+  return l;
+}
+
+bool dims_ok(long U, int C, int width, int height, long max_isect) {  // the forward's limits
+  if (U <= 0 || C <= 0 || width <= 0 || height <= 0 || max_isect <= 0 || max_isect >= (1L << 31)) return false;
+  const long nt = (long)((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
+  return U * (long)C < (1L << 32) && nt * C < (1L << 24);
+}
+
+// ---------------------------------------------------------------------------------------------- projection backward
+// Reverse of sh_eval: gk[k] = dL/d(basis k) -> dL/d(x, y, z) of the unit direction.
+template <int DEG>
+__host__ __device__ __forceinline__ void sh_eval_bwd(float x, float y, float z, const float* gk, float& vx, float& vy, float& vz) {
+  vx = vy = vz = 0.f;
+  if constexpr (DEG >= 1) { vy += -0.48860251190292f * gk[1]; vz += 0.48860251190292f * gk[2]; vx += -0.48860251190292f * gk[3]; }
+  if constexpr (DEG >= 2) {
+    const float z2 = z * z, t0b = -1.092548430592079f * z, c1 = x * x - y * y, s1 = 2.f * x * y;
+    float v_z2 = 0.f, v_c1 = 0.f, v_s1 = 0.f, v_p6 = 0.f;
+    if constexpr (DEG >= 3) {
+      const float t0c = -2.285228997322329f * z2 + 0.4570457994644658f, t1b = 1.445305721320277f * z;
+      const float c2 = x * c1 - y * s1, s2 = x * s1 + y * c1;
+      float v_c2 = 0.f, v_s2 = 0.f, v_p12 = 0.f;
+      if constexpr (DEG >= 4) {
+        const float p12 = z * (1.865881662950577f * z2 - 1.119528997770346f);
+        const float t0d = z * (-4.683325804901025f * z2 + 2.007139630671868f), t1c = 3.31161143515146f * z2 - 0.47308734787878f;
+        const float t2b = -1.770130769779931f * z;
+        const float v_s3 = 0.6258357354491763f * gk[16], v_c3 = 0.6258357354491763f * gk[24];
+        const float v_t2b = gk[17] * s2 + gk[23] * c2;
+        v_s2 += gk[17] * t2b; v_c2 += gk[23] * t2b;
+        const float v_t1c = gk[18] * s1 + gk[22] * c1;
+        v_s1 += gk[18] * t1c; v_c1 += gk[22] * t1c;
+        const float v_t0d = gk[19] * y + gk[21] * x;
+        vy += gk[19] * t0d; vx += gk[21] * t0d;
+        vz += 1.984313483298443f * p12 * gk[20]; v_p12 += 1.984313483298443f * z * gk[20]; v_p6 += -1.006230589874905f * gk[20];
+        vx += c2 * v_c3; v_c2 += x * v_c3; vy += -s2 * v_c3; v_s2 += -y * v_c3;   // c3 = x c2 - y s2
+        vx += s2 * v_s3; v_s2 += x * v_s3; vy += c2 * v_s3; v_c2 += y * v_s3;    // s3 = x s2 + y c2
+        vz += (-4.683325804901025f * z2 + 2.007139630671868f) * v_t0d; v_z2 += -4.683325804901025f * z * v_t0d;
+        v_z2 += 3.31161143515146f * v_t1c;
+        vz += -1.770130769779931f * v_t2b;
+      }
+      v_s2 += -0.5900435899266435f * gk[9]; v_c2 += -0.5900435899266435f * gk[15];
+      const float v_t1b = gk[10] * s1 + gk[14] * c1;
+      v_s1 += gk[10] * t1b; v_c1 += gk[14] * t1b;
+      const float v_t0c = gk[11] * y + gk[13] * x;
+      vy += gk[11] * t0c; vx += gk[13] * t0c;
+      v_p12 += gk[12];
+      vx += c1 * v_c2; v_c1 += x * v_c2; vy += -s1 * v_c2; v_s1 += -y * v_c2;    // c2 = x c1 - y s1
+      vx += s1 * v_s2; v_s1 += x * v_s2; vy += c1 * v_s2; v_c1 += y * v_s2;     // s2 = x s1 + y c1
+      vz += (1.865881662950577f * z2 - 1.119528997770346f) * v_p12; v_z2 += 1.865881662950577f * z * v_p12;
+      v_z2 += -2.285228997322329f * v_t0c;
+      vz += 1.445305721320277f * v_t1b;
+    }
+    v_s1 += 0.5462742152960395f * gk[4]; v_c1 += 0.5462742152960395f * gk[8];
+    const float v_t0b = gk[5] * y + gk[7] * x;
+    vy += gk[5] * t0b; vx += gk[7] * t0b;
+    v_p6 += gk[6];
+    v_z2 += 0.9461746957575601f * v_p6;
+    vx += 2.f * y * v_s1; vy += 2.f * x * v_s1;
+    vx += 2.f * x * v_c1; vy += -2.f * y * v_c1;
+    vz += -1.092548430592079f * v_t0b;
+    vz += 2.f * z * v_z2;
+  }
+}
+
+struct ProjGeo {  // what the forward derives from the call's constants
+  const float* V; const float* Kc; const float* campos;
+  float W, H, eps2d;
+};
+
+// One visible (camera, Gaussian) entry.  m = world mean, sw = upper triangle of the world covariance (00 01 02 11 12 22),
+// s = this Gaussian's SH row, vm2 / vcon / vcol = the entry's incoming gradients.  Adds into vm[3], vS[6] (symmetric dL/dS of the
+// full matrix, same packing) and dsh[3 * NB] (basis-major: dsh[3 k + channel]).
+template <int DEG>
+__host__ __device__ __forceinline__ void proj_bwd_entry(const ProjGeo& q, const float* m, const float* sw, const float* s, int sh_layout,
+                                                        int sh_k, const float* vm2, const float* vcon, const float* vcol, float* vm,
+                                                        float* vS, float* dsh) {
+  constexpr int NB = (DEG + 1) * (DEG + 1);
+  const float* V = q.V;
+  const float R00 = V[0], R01 = V[1], R02 = V[2], R10 = V[4], R11 = V[5], R12 = V[6], R20 = V[8], R21 = V[9], R22 = V[10];
+  const float mx = m[0], my = m[1], mz = m[2];
+  const float x = R00 * mx + R01 * my + R02 * mz + V[3];
+  const float y = R10 * mx + R11 * my + R12 * mz + V[7];
+  const float z = R20 * mx + R21 * my + R22 * mz + V[11];
+  const float s00 = sw[0], s01 = sw[1], s02 = sw[2], s11 = sw[3], s12 = sw[4], s22 = sw[5];
+  // the forward's chain up to the 2D covariance
+  const float a00 = R00 * s00 + R01 * s01 + R02 * s02, a01 = R00 * s01 + R01 * s11 + R02 * s12, a02 = R00 * s02 + R01 * s12 + R02 * s22;
+  const float a10 = R10 * s00 + R11 * s01 + R12 * s02, a11 = R10 * s01 + R11 * s11 + R12 * s12, a12 = R10 * s02 + R11 * s12 + R12 * s22;
+  const float a20 = R20 * s00 + R21 * s01 + R22 * s02, a21 = R20 * s01 + R21 * s11 + R22 * s12, a22 = R20 * s02 + R21 * s12 + R22 * s22;
+  const float c00 = a00 * R00 + a01 * R01 + a02 * R02, c01 = a00 * R10 + a01 * R11 + a02 * R12, c02 = a00 * R20 + a01 * R21 + a02 * R22;
+  const float c11 = a10 * R10 + a11 * R11 + a12 * R12, c12 = a10 * R20 + a11 * R21 + a12 * R22;
+  const float c22 = a20 * R20 + a21 * R21 + a22 * R22;
+  const float fx = q.Kc[0], fy = q.Kc[4], cx = q.Kc[2], cy = q.Kc[5];
+  const float tfx = 0.5f * q.W / fx, tfy = 0.5f * q.H / fy;
+  const float lxp = (q.W - cx) / fx + 0.3f * tfx, lxn = cx / fx + 0.3f * tfx;
+  const float lyp = (q.H - cy) / fy + 0.3f * tfy, lyn = cy / fy + 0.3f * tfy;
+  const float rz = 1.f / z, rz2 = rz * rz;
+  const float xz = x * rz, yz = y * rz;
+  const float cxz = fminf(lxp, fmaxf(-lxn, xz)), cyz = fminf(lyp, fmaxf(-lyn, yz));
+  const float tx = z * cxz, ty = z * cyz;
+  const float j00 = fx * rz, j02 = -fx * tx * rz2, j11 = fy * rz, j12 = -fy * ty * rz2;
+  const float t00 = j00 * c00 + j02 * c02, t01 = j00 * c01 + j02 * c12, t02 = j00 * c02 + j02 * c22;   // J Cc, row 0
+  const float t10 = j11 * c01 + j12 * c02, t11 = j11 * c11 + j12 * c12, t12 = j11 * c12 + j12 * c22;   // row 1
+  const float q00 = t00 * j00 + t02 * j02 + q.eps2d;
+  const float q01 = t01 * j11 + t02 * j12;
+  const float q11 = t11 * j11 + t12 * j12 + q.eps2d;
+  const float id = 1.f / (q00 * q11 - q01 * q01);
+  const float X00 = q11 * id, X01 = -q01 * id, X11 = q00 * id;  // the conic
+  // conic = Q^-1:  dL/dQ = -X G X with G = [[va, vb/2], [vb/2, vc]]  (symmetric 2x2; M01 stands for both off-diagonal positions)
+  const float G00 = vcon[0], G01 = 0.5f * vcon[1], G11 = vcon[2];
+  const float h00 = X00 * G00 + X01 * G01, h01 = X00 * G01 + X01 * G11, h10 = X01 * G00 + X11 * G01, h11 = X01 * G01 + X11 * G11;
+  const float M00 = -(h00 * X00 + h01 * X01), M01 = -(h00 * X01 + h01 * X11), M11 = -(h10 * X01 + h11 * X11);
+  // Q = J Cc J^T + eps:  dL/dCc = J^T M J (symmetric 3x3),  dL/dJ = 2 M (J Cc)
+  const float w00 = j00 * j00 * M00, w01 = j00 * j11 * M01, w02 = j00 * (M00 * j02 + M01 * j12);
+  const float w11 = j11 * j11 * M11, w12 = j11 * (M01 * j02 + M11 * j12);
+  const float w22 = j02 * j02 * M00 + 2.f * j02 * j12 * M01 + j12 * j12 * M11;
+  const float vj00 = 2.f * (M00 * t00 + M01 * t10), vj02 = 2.f * (M00 * t02 + M01 * t12);
+  const float vj11 = 2.f * (M01 * t01 + M11 * t11), vj12 = 2.f * (M01 * t02 + M11 * t12);
+  // Cc = R S R^T:  dL/dS = R^T W R
+  const float b00 = w00 * R00 + w01 * R10 + w02 * R20, b01 = w00 * R01 + w01 * R11 + w02 * R21, b02 = w00 * R02 + w01 * R12 + w02 * R22;
+  const float b10 = w01 * R00 + w11 * R10 + w12 * R20, b11 = w01 * R01 + w11 * R11 + w12 * R21, b12 = w01 * R02 + w11 * R12 + w12 * R22;
+  const float b20 = w02 * R00 + w12 * R10 + w22 * R20, b21 = w02 * R01 + w12 * R11 + w22 * R21, b22 = w02 * R02 + w12 * R12 + w22 * R22;
+  vS[0] += R00 * b00 + R10 * b10 + R20 * b20; vS[1] += R00 * b01 + R10 * b11 + R20 * b21; vS[2] += R00 * b02 + R10 * b12 + R20 * b22;
+  vS[3] += R01 * b01 + R11 * b11 + R21 * b21; vS[4] += R01 * b02 + R11 * b12 + R21 * b22;
+  vS[5] += R02 * b02 + R12 * b12 + R22 * b22;
+  // J, the pixel mean and the depth channel -> camera-space mean
+  float vrz = fx * vj00 + fy * vj11 - 2.f * rz * (fx * tx * vj02 + fy * ty * vj12) + fx * x * vm2[0] + fy * y * vm2[1];
+  const float vtx = -fx * rz2 * vj02, vty = -fy * rz2 * vj12;
+  float vx = fx * rz * vm2[0], vy = fy * rz * vm2[1], vz = cxz * vtx + cyz * vty + vcol[3];
+  if (xz >= -lxn && xz <= lxp) { vx += rz * z * vtx; vrz += x * z * vtx; }   // inside the clamp: tx = z * (x rz)
+  if (yz >= -lyn && yz <= lyp) { vy += rz * z * vty; vrz += y * z * vty; }
+  vz -= rz2 * vrz;
+  vm[0] += R00 * vx + R10 * vy + R20 * vz; vm[1] += R01 * vx + R11 * vy + R21 * vz; vm[2] += R02 * vx + R12 * vy + R22 * vz;
+  // SH colour: clamp_min(c + 0.5, 0) mask, coefficients, and the view direction
+  const float dx = mx - q.campos[0], dy = my - q.campos[1], dz = mz - q.campos[2];
+  const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
+  const float inv = 1.f / fmaxf(nrm, 1e-20f);
+  const float ux = dx * inv, uy = dy * inv, uz = dz * inv;
+  float bas[NB];
+  sh_eval<DEG>(ux, uy, uz, bas);
+  float r = 0.f, gg = 0.f, b = 0.f;
+  if (sh_layout == 0) {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) { r += bas[k] * s[3 * k]; gg += bas[k] * s[3 * k + 1]; b += bas[k] * s[3 * k + 2]; }
+  } else {
+#pragma unroll
+    for (int k = 0; k < NB; ++k) { r += bas[k] * s[k]; gg += bas[k] * s[sh_k + k]; b += bas[k] * s[2 * sh_k + k]; }
+  }
+  const float vr = (r + 0.5f >= 0.f) ? vcol[0] : 0.f, vg = (gg + 0.5f >= 0.f) ? vcol[1] : 0.f, vb = (b + 0.5f >= 0.f) ? vcol[2] : 0.f;
+  float gk[NB];
+#pragma unroll
+  for (int k = 0; k < NB; ++k) {
+    dsh[3 * k] += bas[k] * vr; dsh[3 * k + 1] += bas[k] * vg; dsh[3 * k + 2] += bas[k] * vb;
+    gk[k] = (sh_layout == 0) ? s[3 * k] * vr + s[3 * k + 1] * vg + s[3 * k + 2] * vb : s[k] * vr + s[sh_k + k] * vg + s[2 * sh_k + k] * vb;
+  }
+  float vux, vuy, vuz;
+  sh_eval_bwd<DEG>(ux, uy, uz, gk, vux, vuy, vuz);
+  const float dot = ux * vux + uy * vuy + uz * vuz;  // u = d / |d|:  dL/dd = (v - u (u . v)) / |d|
+  if (nrm >= 1e-20f) { vm[0] += (vux - ux * dot) * inv; vm[1] += (vuy - uy * dot) * inv; vm[2] += (vuz - uz * dot) * inv; }
+}
+
+struct ProjBwdP {
+  const float* means; const float* covars; const float* sh;
+  const float* viewmat; const float* campos; const float* K;
+  int sh_layout, sh_k;
+  int U, C, W, H;
+  float eps2d;
+  const int* radii; const float* d_means2d; const float* d_conics; const float* d_colors; const float* d_opac;
+  float* d_means; float* d_covars; float* d_sh; float* d_opacities;
+};
+
+// One wave = 64 consecutive Gaussians, cameras in index order.  LDS: the SH rows of the 64 Gaussians (as the forward stages them),
+// overwritten at the end by their gradient rows for a coalesced store.
+template <int DEG>
+__global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
+  extern __shared__ float s_sh[];
+  constexpr int NB = (DEG + 1) * (DEG + 1);
+  const int lane = threadIdx.x;
+  const int g0 = blockIdx.x * 64;
+  const int g = g0 + lane;
+  const int row = 3 * p.sh_k;
+  const int nrow = min(64, p.U - g0);
+  const int total = nrow * row;
+  {
+    const float* src = p.sh + (long)g0 * row;
+    for (int i = lane; i < total; i += 64) s_sh[i] = src[i];
+  }
+  __syncthreads();
+  float* s = s_sh + lane * row;
+  if (g < p.U) {
+    float vm[3] = {0.f, 0.f, 0.f}, vS[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, vop = 0.f;
+    float dsh[3 * NB];
+#pragma unroll
+    for (int i = 0; i < 3 * NB; ++i) dsh[i] = 0.f;
+    const float m[3] = {p.means[3L * g], p.means[3L * g + 1], p.means[3L * g + 2]};
+    const float* cv = p.covars + 9L * g;
+    const float sw[6] = {cv[0], cv[1], cv[2], cv[4], cv[5], cv[8]};
+    for (int c = 0; c < p.C; ++c) {
+      const long o = (long)c * p.U + g;
+      if (p.radii[o] <= 0) continue;  // culled entries contribute exactly zero
+      const ProjGeo q = {p.viewmat + 16 * c, p.K + 9 * c, p.campos + 3 * c, (float)p.W, (float)p.H, p.eps2d};
+      const float vm2[2] = {p.d_means2d[2 * o], p.d_means2d[2 * o + 1]};
+      const float vcon[3] = {p.d_conics[3 * o], p.d_conics[3 * o + 1], p.d_conics[3 * o + 2]};
+      const f32x4 vc4 = *(const f32x4*)(p.d_colors + 4 * o);
+      const float vcol[4] = {vc4[0], vc4[1], vc4[2], vc4[3]};
+      proj_bwd_entry<DEG>(q, m, sw, s, p.sh_layout, p.sh_k, vm2, vcon, vcol, vm, vS, dsh);
+      vop += p.d_opac[o];
+    }
+    p.d_means[3L * g] = vm[0]; p.d_means[3L * g + 1] = vm[1]; p.d_means[3L * g + 2] = vm[2];
+    float* dc = p.d_covars + 9L * g;  // "the upper triangle is used": an off-diagonal entry carries both symmetric positions
+    dc[0] = vS[0]; dc[1] = 2.f * vS[1]; dc[2] = 2.f * vS[2];
+    dc[3] = 0.f; dc[4] = vS[3]; dc[5] = 2.f * vS[4];
+    dc[6] = 0.f; dc[7] = 0.f; dc[8] = vS[5];
+    p.d_opacities[g] = vop;
+    // this lane's SH row -> its gradient row (only this lane reads or writes row `lane`)
+    for (int i = 0; i < row; ++i) s[i] = 0.f;
+    if (p.sh_layout == 0) {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) { s[3 * k] = dsh[3 * k]; s[3 * k + 1] = dsh[3 * k + 1]; s[3 * k + 2] = dsh[3 * k + 2]; }
+    } else {
+#pragma unroll
+      for (int k = 0; k < NB; ++k) { s[k] = dsh[3 * k]; s[p.sh_k + k] = dsh[3 * k + 1]; s[2 * p.sh_k + k] = dsh[3 * k + 2]; }
+    }
+  }
+  __syncthreads();
+  float* dst = p.d_sh + (long)g0 * row;
+  for (int i = lane; i < total; i += 64) dst[i] = s_sh[i];
+}
+
+template <int DEG>
+void launch_project_bwd(const ProjBwdP& p, hipStream_t stream) {
+  const size_t lds = (size_t)64 * 3 * p.sh_k * sizeof(float);
+  hipLaunchKernelGGL(gs_project_bwd_kernel<DEG>, dim3((unsigned)((p.U + 63) / 64)), dim3(64), lds, stream, p);
+}
+
+}  // namespace
+
+extern "C" long v3a_gs_rasterize_backward_workspace_bytes(long U, int C, int width, int height, long max_isect) {
+  if (!dims_ok(U, C, width, height, max_isect)) return V3A_ERR_SHAPE;
+  return (long)blayout(U * C, max_isect).total;
+}
+
+extern "C" int v3a_gs_rasterize_backward(const v3a_gs_rasterize_backward_args* a, void* stream_) {
+  if (!a || !a->radii || !a->means2d || !a->conics || !a->colors || !a->opacities || !a->tile_offsets || !a->d_color || !a->d_depth ||
+      !a->d_alpha || !a->d_means2d || !a->d_conics || !a->d_colors || !a->d_opacity_partial || !a->workspace)
+    return V3A_ERR_ARG;
+  if (a->n_isect < 0 || (a->n_isect > 0 && !a->flatten_ids)) return V3A_ERR_ARG;
+  if (!dims_ok(a->U, a->C, a->width, a->height, a->n_isect > 0 ? a->n_isect : 1)) return V3A_ERR_SHAPE;
+  hipStream_t stream = (hipStream_t)stream_;
+  const int tw = (a->width + TILE - 1) / TILE, th = (a->height + TILE - 1) / TILE, ntiles = tw * th;
+  const long CU = a->U * a->C;
+  const int nt_all = ntiles * a->C;
+  const BLayout l = blayout(CU, a->n_isect > 0 ? a->n_isect : 1);
+  if ((size_t)a->workspace_bytes < l.total) return V3A_ERR_WORKSPACE;
+  char* ws = (char*)a->workspace;
+  unsigned int* counts = (unsigned int*)(ws + l.counts);
+  unsigned int* incl = (unsigned int*)(ws + l.incl);
+  float* rows = (float*)(ws + l.rows);
+  const unsigned gb = (unsigned)((CU + 255) / 256);
+  CountP cp = {a->radii, a->means2d, CU, tw, th, counts};
+  hipLaunchKernelGGL(gs_bwd_count_kernel, dim3(gb), dim3(256), 0, stream, cp);
+  size_t tb = l.tmp_bytes;
+  if (rocprim::inclusive_scan(ws + l.tmp, tb, counts, incl, (size_t)CU, rocprim::plus<unsigned int>(), stream) != hipSuccess)
+    return V3A_ERR_LAUNCH;
+  BlendBwdP bp = {a->radii, a->means2d, a->conics, a->colors, a->opacities, a->tile_offsets, a->flatten_ids, counts, incl, a->background,
+                  a->d_color, a->d_depth, a->d_alpha, rows, (unsigned int)a->n_isect, (unsigned int)CU, (int)a->U, a->width, a->height,
+                  tw, th, ntiles, a->clamp_rgb};
+  if (a->n_isect > 0) hipLaunchKernelGGL(gs_blend_bwd_kernel, dim3((unsigned)nt_all), dim3(256), 0, stream, bp);
+  RowSumP rp = {counts, incl, rows, CU, (unsigned int)a->n_isect, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial};
+  hipLaunchKernelGGL(gs_rowsum_kernel, dim3(gb), dim3(256), 0, stream, rp);
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}
+
+extern "C" int v3a_gs_project_backward(const v3a_gs_project_backward_args* a, void* stream) {
+  if (!a || !a->means || !a->covars || !a->sh || !a->viewmat || !a->campos || !a->K || !a->radii || !a->d_means2d || !a->d_conics ||
+      !a->d_colors || !a->d_opacity_partial || !a->d_means || !a->d_covars || !a->d_sh || !a->d_opacities)
+    return V3A_ERR_ARG;
+  if (a->U < 0 || a->C <= 0 || a->width <= 0 || a->height <= 0 || a->U >= (1L << 31)) return V3A_ERR_SHAPE;
+  if (a->sh_degree < 0 || a->sh_degree > 4 || a->sh_k < (a->sh_degree + 1) * (a->sh_degree + 1) || a->sh_k > 64) return V3A_ERR_SHAPE;
+  if (a->sh_layout != 0 && a->sh_layout != 1) return V3A_ERR_ARG;
+  if (a->U == 0) return V3A_OK;
+  ProjBwdP p = {a->means, a->covars, a->sh, a->viewmat, a->campos, a->K, a->sh_layout, a->sh_k, (int)a->U, a->C, a->width, a->height,
+                a->eps2d, a->radii, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial, a->d_means, a->d_covars, a->d_sh,
+                a->d_opacities};
+  hipStream_t st = (hipStream_t)stream;
+  switch (a->sh_degree) {
+    case 0: launch_project_bwd<0>(p, st); break;
+    case 1: launch_project_bwd<1>(p, st); break;
+    case 2: launch_project_bwd<2>(p, st); break;
+    case 3: launch_project_bwd<3>(p, st); break;
+    default: launch_project_bwd<4>(p, st); break;
+  }
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}

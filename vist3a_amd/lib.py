@@ -104,6 +104,30 @@ class GsRasterizeArgs(C.Structure):
     ]
 
 
+class GsRasterizeBackwardArgs(C.Structure):
+    _fields_ = [
+        ("radii", C.c_void_p), ("means2d", C.c_void_p), ("conics", C.c_void_p), ("colors", C.c_void_p),
+        ("opacities", C.c_void_p), ("background", C.c_void_p),
+        ("U", C.c_long), ("C", C.c_int), ("width", C.c_int), ("height", C.c_int), ("clamp_rgb", C.c_int),
+        ("tile_offsets", C.c_void_p), ("flatten_ids", C.c_void_p), ("n_isect", C.c_long),
+        ("d_color", C.c_void_p), ("d_depth", C.c_void_p), ("d_alpha", C.c_void_p),
+        ("d_means2d", C.c_void_p), ("d_conics", C.c_void_p), ("d_colors", C.c_void_p), ("d_opacity_partial", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
+class GsProjectBackwardArgs(C.Structure):
+    _fields_ = [
+        ("means", C.c_void_p), ("covars", C.c_void_p), ("sh", C.c_void_p),
+        ("sh_layout", C.c_int), ("sh_k", C.c_int), ("sh_degree", C.c_int),
+        ("viewmat", C.c_void_p), ("campos", C.c_void_p), ("K", C.c_void_p),
+        ("U", C.c_long), ("C", C.c_int), ("width", C.c_int), ("height", C.c_int), ("eps2d", C.c_float),
+        ("radii", C.c_void_p),
+        ("d_means2d", C.c_void_p), ("d_conics", C.c_void_p), ("d_colors", C.c_void_p), ("d_opacity_partial", C.c_void_p),
+        ("d_means", C.c_void_p), ("d_covars", C.c_void_p), ("d_sh", C.c_void_p), ("d_opacities", C.c_void_p),
+    ]
+
+
 
 class AttnArgs(C.Structure):
     _fields_ = [
@@ -244,7 +268,10 @@ SYMBOLS = {
     "v3a_gs_project": (C.c_int, [C.POINTER(GsProjectArgs), C.c_void_p]),
     "v3a_gs_rasterize_workspace_bytes": (C.c_long, [C.c_long, C.c_int, C.c_int, C.c_int, C.c_long]),
     "v3a_gs_rasterize": (C.c_int, [C.POINTER(GsRasterizeArgs), C.c_void_p]),
-    "v3a_softmax_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "v3a_gs_rasterize_backward_workspace_bytes": (C.c_long, [C.c_long, C.c_int, C.c_int, C.c_int, C.c_long]),
+    "v3a_gs_rasterize_backward": (C.c_int, [C.POINTER(GsRasterizeBackwardArgs), C.c_void_p]),
+    "v3a_gs_project_backward": (C.c_int, [C.POINTER(GsProjectBackwardArgs), C.c_void_p]),
+    "v3a_softmax_rows":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "v3a_image_metrics_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "v3a_image_metrics": (C.c_int, [C.POINTER(ImageMetricsArgs), C.c_void_p]),
     "v3a_lpips_input": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 3),
@@ -254,7 +281,7 @@ SYMBOLS = {
 }
 
 _lib = None
-EXPECTED_ABI = 23   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 24   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

@@ -5,7 +5,12 @@ with color [B,V,3,H,W] in [0,1], depth [B,V,H,W] (alpha-weighted z, not normalis
 
 As in the reference: extrinsics are camera-to-world, intrinsics are normalised (row 0 x W, row 1 x H), `near`/`far` are
 accepted and ignored (gsplat is called with near_plane=1e-10 and its default far plane), SH degree comes from the harmonics
-width, the world covariances are passed explicitly, background = cfg.background_color on RGB only."""
+width, the world covariances are passed explicitly, background = cfg.background_color on RGB only.
+
+Differentiable like gsplat's renderer: when grad mode is on and any of `gaussians.means / covariances / harmonics / opacities`
+requires grad, the camera batches go through `ops.gs_render` (HIP backward kernels, csrc/raster_bwd.hip) and color / depth / alpha
+carry the graph back to the Gaussians.  The forward values are the same kernels' either way.  Cameras are constants: extrinsics or
+intrinsics that require grad raise NotImplementedError (gsplat's optional pose gradients are not implemented)."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -44,6 +49,11 @@ class DecoderSplattingCUDA:
         H, W = image_shape
         dev = self.device
         self.last_n_isect = []
+        need_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (gaussians.means, gaussians.covariances, gaussians.harmonics,
+                                                                                 gaussians.opacities))
+        if torch.is_grad_enabled() and (extrinsics.requires_grad or intrinsics.requires_grad):
+            raise NotImplementedError("DecoderSplattingCUDA: gradients to extrinsics / intrinsics (camera pose gradients) are not "
+                                      "implemented; detach them, or the result would silently lack that branch of the graph")
         imgs, depths, alphas = [], [], []
         for i in range(B):
             means = gaussians.means[i].float().contiguous()
@@ -61,6 +71,14 @@ class DecoderSplattingCUDA:
             ci, di, ai = [], [], []
             for j0 in range(0, V, self.camera_batch):  # the reference renders one camera per call; same arithmetic, batched
                 sl = slice(j0, min(j0 + self.camera_batch, V))
+                if need_grad:
+                    c_, d_, a_ = ops.gs_render(means, cov, sh, op, w2c_d[sl].contiguous(), cam_d[sl].contiguous(), K_d[sl].contiguous(),
+                                               W, H, sh_degree=sh_degree, sh_layout=1, background=self.background_color, clamp_rgb=True,
+                                               workspace=self._ws, n_isect_out=self.last_n_isect)
+                    ci.append(c_.permute(0, 3, 1, 2))
+                    di.append(d_)
+                    ai.append(a_)
+                    continue
                 pr = ops.gs_project(means, cov, sh, w2c_d[sl].contiguous(), cam_d[sl].contiguous(), K_d[sl].contiguous(), W, H,
                                     sh_degree=sh_degree, sh_layout=1, near_plane=1e-10, far_plane=1e10, radius_clip=0.1, eps2d=0.3)
                 r = ops.gs_rasterize(pr, op, W, H, background=self.background_color, clamp_rgb=True, workspace=self._ws)

@@ -991,6 +991,7 @@ class GsWorkspace:
 
     def __init__(self):
         self.buf, self.cap, self.key = None, 0, None
+        self.bwd = None  # GsBwdWorkspace, created by the first gs_render backward that is handed this workspace
 
     def get(self, U, Cn, width, height, need):
         key = (U, Cn, width, height)
@@ -1043,6 +1044,148 @@ def gs_rasterize(proj: dict, opacities: torch.Tensor, width: int, height: int, *
     if return_order:
         out["tile_offsets"], out["flatten_ids"] = offs, ids[: n_host.value]
     return out
+
+
+class GsBwdWorkspace:
+    """Grow-only scratch for v3a_gs_rasterize_backward: two counters per camera-Gaussian entry and one 48-byte row per
+    intersection (the price of summing without atomics: every (Gaussian, tile) contribution is stored once, then added in order)."""
+
+    def __init__(self):
+        self.buf, self.cap, self.key = None, 0, None
+
+    def get(self, U, Cn, width, height, need):
+        key = (U, Cn, width, height)
+        if self.buf is None or self.key != key or need > self.cap:
+            self.cap = max(int(need * 1.25), 1 << 16)
+            nbytes = L.load().v3a_gs_rasterize_backward_workspace_bytes(U, Cn, width, height, self.cap)
+            if nbytes < 0:
+                L.check(int(nbytes), "v3a_gs_rasterize_backward_workspace_bytes")
+            self.buf, self.key = None, key
+            self.buf = torch.empty(nbytes, device="cuda", dtype=torch.uint8)
+        return self.buf
+
+
+def _gs_f32(t: torch.Tensor, name: str, numel: int) -> None:
+    if t.dtype != f32 or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError(f"{name}: contiguous fp32 device tensor of {numel} elements required, got {t.dtype} {tuple(t.shape)}")
+
+
+def gs_rasterize_backward(proj: dict, opacities: torch.Tensor, width: int, height: int, tile_offsets: torch.Tensor,
+                          flatten_ids: torch.Tensor, d_color: torch.Tensor, d_depth: torch.Tensor, d_alpha: torch.Tensor, *,
+                          background: Optional[torch.Tensor] = None, clamp_rgb: bool = True,
+                          workspace: Optional[GsBwdWorkspace] = None):
+    """Backward of gs_rasterize: `proj` and (tile_offsets, flatten_ids) as the forward had / returned them (return_order=True),
+    d_color [C,H,W,3], d_depth, d_alpha [C,H,W] -> dict(d_means2d [C,U,2], d_conics [C,U,3], d_colors [C,U,4], d_opacity [C,U])
+    per camera-Gaussian entry; without the C axis when `proj` came from a single-camera gs_project call."""
+    U, dev = opacities.shape[0], opacities.device
+    if U == 0:
+        raise ValueError("no Gaussians to draw")
+    single = proj["radii"].dim() == 1
+    Cn = 1 if single else proj["radii"].shape[0]
+    lead = () if single else (Cn,)
+    ntiles = ((width + 15) // 16) * ((height + 15) // 16)
+    _gs_f32(opacities, "opacities", U)
+    for k, n in (("means2d", 2), ("conics", 3), ("colors", 4)):
+        _gs_f32(proj[k], k, Cn * U * n)
+    if proj["radii"].dtype != torch.int32 or not proj["radii"].is_contiguous() or proj["radii"].numel() != Cn * U:
+        raise ValueError("radii: contiguous int32 [C,U] required")
+    _gs_f32(d_color, "d_color", Cn * height * width * 3)
+    _gs_f32(d_depth, "d_depth", Cn * height * width)
+    _gs_f32(d_alpha, "d_alpha", Cn * height * width)
+    if background is not None:
+        _gs_f32(background, "background", 3)
+    if tile_offsets.dtype != torch.int32 or not tile_offsets.is_contiguous() or tile_offsets.numel() != Cn * ntiles + 1:
+        raise ValueError(f"tile_offsets: contiguous int32 [{Cn * ntiles + 1}] required")
+    if flatten_ids.dtype != torch.int32 or not flatten_ids.is_contiguous():
+        raise ValueError("flatten_ids: contiguous int32 required")
+    n_isect = flatten_ids.numel()
+    wsp = workspace or GsBwdWorkspace()
+    buf = wsp.get(U, Cn, width, height, max(n_isect, 1))
+    e = lambda *s: torch.empty(*lead, *s, device=dev, dtype=f32)
+    dm2, dcon, dcol, dop = e(U, 2), e(U, 3), e(U, 4), e(U)
+    a = L.GsRasterizeBackwardArgs(_ptr(proj["radii"]), _ptr(proj["means2d"]), _ptr(proj["conics"]), _ptr(proj["colors"]), _ptr(opacities),
+                                  _ptr(background) if background is not None else None, U, Cn, width, height, int(clamp_rgb),
+                                  _ptr(tile_offsets), _ptr(flatten_ids) if n_isect else None, n_isect, _ptr(d_color), _ptr(d_depth),
+                                  _ptr(d_alpha), _ptr(dm2), _ptr(dcon), _ptr(dcol), _ptr(dop), _ptr(buf), buf.numel())
+    L.check(L.load().v3a_gs_rasterize_backward(C.byref(a), _stream()), "v3a_gs_rasterize_backward")
+    return dict(d_means2d=dm2, d_conics=dcon, d_colors=dcol, d_opacity=dop)
+
+
+def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, viewmat: torch.Tensor, campos: torch.Tensor,
+                        K: torch.Tensor, width: int, height: int, radii: torch.Tensor, entry_grads: dict, *, sh_degree: int = 4,
+                        sh_layout: int = 1, eps2d: float = 0.3):
+    """Backward of gs_project: the entry gradients of gs_rasterize_backward (or any dict with d_means2d, d_conics, d_colors,
+    d_opacity) -> (d_means [U,3], d_covars [U,3,3], d_sh like sh, d_opacities [U]), summed over the cameras in index order.
+    Cameras are constants: there is no gradient for viewmat / campos / K."""
+    for t, n in ((means, "means"), (covars, "covars"), (sh, "sh"), (viewmat, "viewmat"), (campos, "campos"), (K, "K")):
+        if t.dtype != f32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{n}: contiguous fp32 device tensor required")
+    Cn = 1 if viewmat.dim() == 2 else viewmat.shape[0]
+    if campos.numel() != 3 * Cn or K.numel() != 9 * Cn or viewmat.numel() != 16 * Cn:
+        raise ValueError("viewmat / campos / K disagree on the number of cameras")
+    U = means.shape[0]
+    sh_k = sh.shape[2] if sh_layout == 1 else sh.shape[1]
+    if covars.numel() != 9 * U or sh.numel() != 3 * sh_k * U:
+        raise ValueError("means / covars / sh disagree on the number of Gaussians")
+    if radii.dtype != torch.int32 or not radii.is_contiguous() or radii.numel() != Cn * U:
+        raise ValueError("radii: contiguous int32 [C,U] required")
+    for k, n in (("d_means2d", 2), ("d_conics", 3), ("d_colors", 4), ("d_opacity", 1)):
+        _gs_f32(entry_grads[k], k, Cn * U * n)
+    d_means, d_covars, d_sh = torch.empty_like(means), torch.empty_like(covars), torch.empty_like(sh)
+    d_op = torch.empty(U, device=means.device, dtype=f32)
+    a = L.GsProjectBackwardArgs(_ptr(means), _ptr(covars), _ptr(sh), sh_layout, sh_k, sh_degree, _ptr(viewmat), _ptr(campos), _ptr(K), U, Cn,
+                                width, height, eps2d, _ptr(radii), _ptr(entry_grads["d_means2d"]), _ptr(entry_grads["d_conics"]),
+                                _ptr(entry_grads["d_colors"]), _ptr(entry_grads["d_opacity"]), _ptr(d_means), _ptr(d_covars), _ptr(d_sh),
+                                _ptr(d_op))
+    L.check(L.load().v3a_gs_project_backward(C.byref(a), _stream()), "v3a_gs_project_backward")
+    return d_means, d_covars, d_sh, d_op
+
+
+class _GsRender(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, covars, sh, opacities, viewmat, campos, K, width, height, sh_degree, sh_layout, background, clamp_rgb,
+                workspace, n_isect_out):
+        pr = gs_project(means, covars, sh, viewmat, campos, K, width, height, sh_degree=sh_degree, sh_layout=sh_layout)
+        r = gs_rasterize(pr, opacities, width, height, background=background, clamp_rgb=clamp_rgb, workspace=workspace, return_order=True)
+        if n_isect_out is not None:
+            n_isect_out.append(r["n_isect"])
+        ctx.save_for_backward(means, covars, sh, opacities, viewmat, campos, K, pr["radii"], pr["means2d"], pr["conics"], pr["colors"],
+                              r["tile_offsets"], r["flatten_ids"].contiguous())
+        ctx.cfg = (width, height, sh_degree, sh_layout, background, clamp_rgb, workspace)
+        return r["color"], r["depth"], r["alpha"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_color, d_depth, d_alpha):
+        means, covars, sh, opacities, viewmat, campos, K, radii, means2d, conics, colors, offs, ids = ctx.saved_tensors
+        width, height, sh_degree, sh_layout, background, clamp_rgb, workspace = ctx.cfg
+        Cn = radii.shape[0]
+        z = lambda g, *s: torch.zeros(Cn, height, width, *s, device=means.device, dtype=f32) if g is None else g.float().contiguous()
+        if workspace is not None and workspace.bwd is None:
+            workspace.bwd = GsBwdWorkspace()
+        pr = dict(radii=radii, means2d=means2d, conics=conics, colors=colors)
+        eg = gs_rasterize_backward(pr, opacities, width, height, offs, ids, z(d_color, 3), z(d_depth), z(d_alpha), background=background,
+                                   clamp_rgb=clamp_rgb, workspace=workspace.bwd if workspace is not None else None)
+        d_means, d_covars, d_sh, d_op = gs_project_backward(means, covars, sh, viewmat, campos, K, width, height, radii, eg,
+                                                            sh_degree=sh_degree, sh_layout=sh_layout)
+        return (d_means, d_covars, d_sh, d_op) + (None,) * 11
+
+
+def gs_render(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, opacities: torch.Tensor, viewmat: torch.Tensor,
+              campos: torch.Tensor, K: torch.Tensor, width: int, height: int, *, sh_degree: int = 4, sh_layout: int = 1,
+              background: Optional[torch.Tensor] = None, clamp_rgb: bool = True, workspace: Optional[GsWorkspace] = None,
+              n_isect_out: Optional[list] = None):
+    """Differentiable gs_project + gs_rasterize for C cameras (viewmat [C,4,4], campos [C,3], K [C,3,3]) ->
+    (color [C,H,W,3], depth [C,H,W], alpha [C,H,W]) with gradients to means, covars, sh and opacities through the HIP backward
+    kernels (csrc/raster_bwd.hip).  The forward values are gs_rasterize's, bit for bit.  Cameras are constants (gsplat's optional
+    pose gradients are not implemented): viewmat / campos / K that require grad are refused.  First-order only."""
+    for t, n in ((viewmat, "viewmat"), (campos, "campos"), (K, "K")):
+        if t.requires_grad:
+            raise NotImplementedError(f"gs_render: no gradient for {n} (camera pose / intrinsics gradients are not implemented)")
+    if viewmat.dim() != 3:
+        raise ValueError("gs_render: viewmat [C,4,4], campos [C,3], K [C,3,3] required")
+    return _GsRender.apply(means, covars, sh, opacities, viewmat, campos, K, width, height, sh_degree, sh_layout, background,
+                           clamp_rgb, workspace, n_isect_out)
 
 
 def image_metrics(a_u8: torch.Tensor, b_u8: torch.Tensor):
