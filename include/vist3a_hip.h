@@ -23,7 +23,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 24) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 25) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -41,7 +41,8 @@ enum {
   V3A_ACT_GELU_TANH = 1, /* FeedForward(activation_fn="gelu-approximate") */
   V3A_ACT_GELU_ERF = 2,  /* vggt/layers/mlp.py nn.GELU */
   V3A_ACT_SILU = 3,
-  V3A_ACT_RELU = 4
+  V3A_ACT_RELU = 4,
+  V3A_ACT_QUICK_GELU = 5 /* x * sigmoid(1.702 x): CLIP's MLP; the fp32 epilogue of v3a_conv_split only */
 };
 enum {
   V3A_GEMM_BIAS_ROW = 1 << 0,     /* bias indexed by output row (used for the V^T = Wv.X^T form) */
@@ -176,7 +177,7 @@ long v3a_conv_halo_tiles(const v3a_conv_args* args);   /* workgroups the halo ke
  * accumulation,  xl.wh + xh.wl + xh.wh  (the dropped xl.wl term is <= 2^-16 relative), laid out ALONG K of one implicit GEMM:
  *   w[Cout][Kpad]: three consecutive copies of the tap-major K range of v3a_conv_args, holding (wh | wl | wh);
  *   ktab: the chunk table of the three ranges, bit 28 set where the chunk reads the LO plane of x (first range), clear for the hi plane.
- * Everything that follows the accumulation stays in fp32: v = act(acc + bias) (act NONE or RELU) + residual + residual2 ; [RELU_OUT] ;
+ * Everything that follows the accumulation stays in fp32: v = act(acc + bias) (act NONE, RELU or QUICK_GELU) + residual + residual2 ; [RELU_OUT] ;
  * stored as f32 (V3A_GEMM_OUT_F32) or split into the (y, y_lo) planes.  residual: f32 [.., ldr] with V3A_GEMM_RES_F32 (a table, see
  * res_row_mod) else a pair (c.residual, residual_lo); residual2: a pair.  c.scale must be NULL.  Geometry fields (T..pW, ups2, replicate,
  * ldy, out_row_*) as in v3a_conv_args; both planes of a pair share strides.
@@ -571,6 +572,45 @@ int v3a_lpips_pool(const void* x_hi, const void* x_lo, void* y_hi, void* y_lo, i
 long v3a_lpips_head_workspace_bytes(int N, int h, int w, int C);
 int v3a_lpips_head(const void* x_hi, const void* x_lo, const float* weight, int N, int h, int w, int C, double* out, int accumulate,
                    void* workspace, long workspace_bytes, void* stream);
+
+/* ---- CLIP score of the generated-scene evaluation (evaluation/gen_eval/t3_scene_evaluation.py:97-120 of the reference: torchmetrics
+ * CLIPScore on a Hugging Face CLIPModel).  The towers' linear layers are v3a_conv_split (1x1, act QUICK_GELU for fc1), their LayerNorms
+ * v3a_layernorm / v3a_layernorm_pair; these are the passes around them (csrc/clip.hip).
+ *   v3a_clip_preprocess  CLIPImageProcessor on the Pillow path for N uint8 frames [N,H,W,3]: BICUBIC resize exactly as Pillow's
+ *                        ImagingResample does it for 8-bit channels (horizontal pass, rounded and clipped to uint8, then vertical pass; per
+ *                        output sample clip8(((1 << 21) + sum k_i p_i) >> 22)), the centre crop to S x S, the value table lut [3][256]
+ *                        (rescale and normalise in fp32, built by the host) and the patch matrix [N (S/P)^2][ldk] as a (hi, lo) pair:
+ *                        column c P^2 + py P + px, columns 3 P^2 .. ldk zero (ldk % 8 == 0).  The host passes, for the S kept columns and
+ *                        the S kept rows, Pillow's bounds [S][2] (first input sample, tap count) and 22-bit fixed-point coefficients
+ *                        [S][kx] / [S][ky], and the input rows the vertical taps read: row0 .. row0 + rows.  Every bound must lie inside
+ *                        the image / that row range - the tables live on the device, so this entry point CANNOT check them: a caller
+ *                        with mismatched tables reads out of bounds (vist3a_amd.ops.clip_preprocess checks them on the host).  out_u8 [N,S,S,3] and out_f32 [N,3,S,S] are optional copies of the crop.
+ *                        workspace: v3a_clip_preprocess_workspace_bytes(N, rows, S).
+ *   v3a_clip_rows        token assembly, f32 rows of d (d % 4 == 0): out[r] = src[row(r)] + pos[r % S] (pos may be NULL), r < M;
+ *                        row(r) = ids[r] (clamped to src_rows) when ids is given; else with cls given the class token at r % S == 0 and
+ *                        src row r - r / S - 1 elsewhere (src = [M / S][S - 1][d]); else r.
+ *   v3a_attention_f32    softmax(scale q k^T) v in fp32 for B sequences of S <= 1024 rows and H heads of hd = 64 (any other hd:
+ *                        V3A_ERR_SHAPE).  q, k, v: f32, row b S + s at stride ld, head h at column 64 h.  causal != 0 masks keys > query;
+ *                        lens [B] (or NULL) masks keys >= lens[b].  Output row stride ldo: f32 (o_f32) and / or a (hi, lo) pair.  Products
+ *                        and the softmax accumulate in fp32, a row's keys in index order on one lane: bit-reproducible, independent of B.
+ *   v3a_clip_score       fp64: scores[f] = max(100 cos(image_emb[f], text_emb), 0), f < F, embeddings f32 of D; *mean (may be NULL) =
+ *                        their mean, summed in frame order.  A zero embedding gives NaN, as torchmetrics does.  One workgroup, no atomics. */
+typedef struct {
+  const void* src;
+  const int* x_bounds; const int* x_coeffs; const int* y_bounds; const int* y_coeffs;
+  const float* lut;
+  void* patches_hi; void* patches_lo;
+  void* out_u8; float* out_f32;
+  int N, H, W, S, P, ldk, kx, ky, row0, rows;
+  void* workspace; long workspace_bytes;
+} v3a_clip_preprocess_args;
+long v3a_clip_preprocess_workspace_bytes(int N, int rows, int S);
+int v3a_clip_preprocess(const v3a_clip_preprocess_args* args, void* stream);
+int v3a_clip_rows(const float* src, int src_rows, const int* ids, const float* cls, const float* pos, float* out, long M, int S, int d,
+                  void* stream);
+int v3a_attention_f32(const float* q, const float* k, const float* v, int ld, void* o_hi, void* o_lo, float* o_f32, int ldo,
+                      const int* lens, int B, int S, int H, int hd, float scale, int causal, void* stream);
+int v3a_clip_score(const float* image_emb, const float* text_emb, int F, int D, double* scores, double* mean, void* stream);
 
 #ifdef __cplusplus
 }

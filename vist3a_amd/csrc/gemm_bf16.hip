@@ -1128,7 +1128,7 @@ extern "C" int v3a_conv_split(const v3a_conv_split_args* s, void* stream) {
   if (a->Cin % 8 || a->Cout % 8 || a->Kpad % 64 || a->ldy % 8 || a->Kpad / 8 > 4096) return V3A_ERR_SHAPE;
   if ((long)a->oT * a->oH * a->oW > 0x7fffffffL) return V3A_ERR_SHAPE;
   if (a->flags & ~(V3A_GEMM_RES_F32 | V3A_GEMM_OUT_F32 | V3A_GEMM_RELU_OUT)) return V3A_ERR_ARG;
-  if (a->act != V3A_ACT_NONE && a->act != V3A_ACT_RELU) return V3A_ERR_ARG;
+  if (a->act != V3A_ACT_NONE && a->act != V3A_ACT_RELU && a->act != V3A_ACT_QUICK_GELU) return V3A_ERR_ARG;
   if (a->scale) return V3A_ERR_ARG;
   if (!(a->flags & V3A_GEMM_OUT_F32) && !s->y_lo) return V3A_ERR_ARG;
   if (a->residual && ((a->ldr % 8) || (!(a->flags & V3A_GEMM_RES_F32) && !s->residual_lo))) return V3A_ERR_ARG;

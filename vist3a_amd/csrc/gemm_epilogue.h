@@ -389,7 +389,7 @@ __device__ __forceinline__ void add_pair8(const u32x4 hi, const u32x4 lo, float*
 
 // Epilogue of the split-bf16 convolution (v3a_conv_split): nothing is rounded to bf16 on the way.  The wave parks one 32-row group of
 // fp32 accumulators (bias added, ReLU applied) in its private LDS region, re-reads whole rows and finishes 8 columns per lane:
-//   v = act(acc + bias) + residual (f32 table, or a (hi, lo) pair) + residual2 (pair) ; [ReLU] ; store f32, or split into the (hi, lo) planes.
+//   v = act(acc + bias) (ReLU before the park, QUICK_GELU after the re-read) + residual (f32 table, or a (hi, lo) pair) + residual2 (pair) ; [ReLU] ; store f32, or split into the (hi, lo) planes.
 template <int MT, int NTL>
 __device__ __forceinline__ void gemm_epilogue_f32(const GemmP& p, f32x16 (&acc)[MT][NTL], char* smem, int wave, int lane, int mw0, int nw,
                                                   int gstride = 32) {   // gstride: output rows between the wave's 32-row groups (halo tiles: W)
@@ -399,7 +399,7 @@ __device__ __forceinline__ void gemm_epilogue_f32(const GemmP& p, f32x16 (&acc)[
   const int hi = lane >> 5, l31 = lane & 31;
   char* reg = smem + wave * (32 * PITCH);
   const int flags = p.flags;
-  const bool relu_in = p.act == V3A_ACT_RELU, res_f32 = (flags & V3A_GEMM_RES_F32) != 0;
+  const bool relu_in = p.act == V3A_ACT_RELU, quick_gelu = p.act == V3A_ACT_QUICK_GELU, res_f32 = (flags & V3A_GEMM_RES_F32) != 0;
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     const int mw = mw0 + i * gstride;
@@ -440,6 +440,10 @@ __device__ __forceinline__ void gemm_epilogue_f32(const GemmP& p, f32x16 (&acc)[
       float v[8];
 #pragma unroll
       for (int e = 0; e < 4; ++e) { v[e] = a[e]; v[4 + e] = b[e]; }
+      if (quick_gelu) {   // CLIP's MLP: x * sigmoid(1.702 x), fp32 with an IEEE division
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = v[e] / (1.0f + expf(-1.702f * v[e]));
+      }
       if (p.res) {
         if (res_f32) {
 #pragma unroll

@@ -13,7 +13,7 @@ LIB_PATH = Path(os.environ.get("V3A_LIB") or _HERE / "libvist3a_hip.so")   # V3A
 V3A_OK = 0
 ERRORS = {-1: "V3A_ERR_ARG", -2: "V3A_ERR_SHAPE", -3: "V3A_ERR_LAUNCH", -4: "V3A_ERR_WORKSPACE"}
 
-ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU, ACT_RELU = 0, 1, 2, 3, 4
+ACT_NONE, ACT_GELU_TANH, ACT_GELU_ERF, ACT_SILU, ACT_RELU, ACT_QUICK_GELU = 0, 1, 2, 3, 4, 5
 GEMM_BIAS_ROW = 1 << 0
 GEMM_SCALE_PER_BATCH = 1 << 1
 GEMM_ROUND_AFTER_SCALE = 1 << 2
@@ -155,6 +155,16 @@ class XattnProbsArgs(C.Structure):
     ]
 
 
+class ClipPreprocessArgs(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("x_bounds", C.c_void_p), ("x_coeffs", C.c_void_p), ("y_bounds", C.c_void_p), ("y_coeffs", C.c_void_p),
+        ("lut", C.c_void_p), ("patches_hi", C.c_void_p), ("patches_lo", C.c_void_p), ("out_u8", C.c_void_p), ("out_f32", C.c_void_p),
+        ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("S", C.c_int), ("P", C.c_int), ("ldk", C.c_int), ("kx", C.c_int), ("ky", C.c_int),
+        ("row0", C.c_int), ("rows", C.c_int),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
 class GemmFp8Args(C.Structure):
     _fields_ = [("g", GemmArgs), ("a_scale", C.c_void_p), ("b_scale", C.c_void_p)]
 
@@ -278,10 +288,16 @@ SYMBOLS = {
     "v3a_lpips_pool": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
     "v3a_lpips_head_workspace_bytes": (C.c_long, [C.c_int] * 4),
     "v3a_lpips_head": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_void_p]),
+    "v3a_clip_preprocess_workspace_bytes": (C.c_long, [C.c_int] * 3),
+    "v3a_clip_preprocess": (C.c_int, [C.POINTER(ClipPreprocessArgs), C.c_void_p]),
+    "v3a_clip_rows": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_long, C.c_int, C.c_int, C.c_void_p]),
+    "v3a_attention_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4
+                          + [C.c_float, C.c_int, C.c_void_p]),
+    "v3a_clip_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 24   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 25   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

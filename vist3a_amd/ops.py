@@ -1261,3 +1261,115 @@ def lpips_head(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor, accumul
     L.check(lib.v3a_lpips_head(_ptr(x[0]), _ptr(x[1]), _ptr(weight), N, h, w, Cc, _ptr(out), int(accumulate), _ptr(ws), ws.numel(),
                                _stream()), "v3a_lpips_head")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ CLIP score passes (csrc/clip.hip)
+def _dev(t: torch.Tensor, name: str, dtype, dim: Optional[int] = None) -> None:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
+    if t.dtype != dtype or not t.is_contiguous() or (dim is not None and t.dim() != dim):
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor" + (f" of {dim} dimensions" if dim else "")
+                         + f", got {t.dtype} {tuple(t.shape)}")
+
+
+def clip_preprocess(frames: torch.Tensor, tables: dict, lut: torch.Tensor, image_size: int, patch: int, *, want_u8: bool = False,
+                    want_f32: bool = False):
+    """CLIPImageProcessor (Pillow BICUBIC shorter-edge resize, centre crop, rescale, normalise) + patchify for uint8 frames [N,H,W,3].
+    tables: device int32 tensors of evaluation.clip.resize_tables(H, W, image_size) - x_bounds / y_bounds [S,2], x_coeffs / y_coeffs
+    [S,k] - and the ints row0, rows; lut: f32 [3,256].  -> (patch pair [2, N (S/P)^2, ldk], uint8 crop [N,S,S,3] or None, f32 pixel
+    values [N,3,S,S] or None)."""
+    _dev(frames, "frames", torch.uint8, 4)
+    N, H, W, Cc = frames.shape
+    S, P = image_size, patch
+    if Cc != 3:
+        raise ValueError(f"frames must be RGB [N,H,W,3], got {tuple(frames.shape)}")
+    if S % P:
+        raise ValueError(f"image_size {S} is not a multiple of the patch size {P}")
+    _dev(lut, "lut", f32)
+    if lut.numel() != 768:
+        raise ValueError("lut must be f32 [3,256]")
+    for key in ("x_bounds", "y_bounds", "x_coeffs", "y_coeffs"):
+        _dev(tables[key], key, torch.int32, 2)
+        if tables[key].shape[0] != S:
+            raise ValueError(f"{key} must have {S} rows")
+    if tuple(tables["size"]) != (H, W, S):
+        raise ValueError(f"tables were built for {tables['size']}, frames are {(H, W, S)}")
+    row0, rows = int(tables["row0"]), int(tables["rows"])
+    ldk = (3 * P * P + 7) // 8 * 8
+    G = S // P
+    patches = torch.empty((2, N * G * G, ldk), device=frames.device, dtype=bf16)
+    u8 = torch.empty((N, S, S, 3), device=frames.device, dtype=torch.uint8) if want_u8 else None
+    pix = torch.empty((N, 3, S, S), device=frames.device, dtype=f32) if want_f32 else None
+    lib = L.load()
+    need = lib.v3a_clip_preprocess_workspace_bytes(N, rows, S)
+    if need < 0:
+        L.check(int(need), "v3a_clip_preprocess_workspace_bytes")
+    ws = torch.empty(int(need), device=frames.device, dtype=torch.uint8)
+    args = L.ClipPreprocessArgs(_ptr(frames), _ptr(tables["x_bounds"]), _ptr(tables["x_coeffs"]), _ptr(tables["y_bounds"]),
+                                _ptr(tables["y_coeffs"]), _ptr(lut), _ptr(patches[0]), _ptr(patches[1]), _ptr(u8), _ptr(pix),
+                                N, H, W, S, P, ldk, tables["x_coeffs"].shape[1], tables["y_coeffs"].shape[1], row0, rows,
+                                _ptr(ws), ws.numel())
+    L.check(lib.v3a_clip_preprocess(C.byref(args), _stream()), "v3a_clip_preprocess")
+    return patches, u8, pix
+
+
+def clip_rows(src: torch.Tensor, *, ids: Optional[torch.Tensor] = None, cls: Optional[torch.Tensor] = None,
+              pos: Optional[torch.Tensor] = None, S: int = 1, M: Optional[int] = None) -> torch.Tensor:
+    """token assembly into the f32 residual stream: out[r] = src[row(r)] + pos[r % S]; row(r) = ids[r] (int32, inside src), or with
+    `cls` the class token at r % S == 0 and patch row r - r // S - 1 elsewhere (src [B (S-1), d]) -> f32 [M, d]"""
+    _dev(src, "src", f32, 2)
+    d = src.shape[1]
+    if d % 4:
+        raise ValueError("row width must be a multiple of 4")
+    if ids is not None:
+        _dev(ids, "ids", torch.int32)
+        M = ids.numel()
+    elif cls is not None:
+        _dev(cls, "cls", f32)
+        if cls.numel() != d or S < 2 or src.shape[0] % (S - 1):
+            raise ValueError(f"cls must be f32 [{d}] and src hold whole sequences of {S - 1} patch rows")
+        M = src.shape[0] // (S - 1) * S
+    elif M is None:
+        M = src.shape[0]
+    if pos is not None:
+        _dev(pos, "pos", f32, 2)
+        if pos.shape[0] < S or pos.shape[1] != d:
+            raise ValueError(f"pos must be f32 [>= {S}, {d}]")
+    out = torch.empty((M, d), device=src.device, dtype=f32)
+    L.check(L.load().v3a_clip_rows(_ptr(src), src.shape[0], _ptr(ids), _ptr(cls), _ptr(pos), _ptr(out), M, S, d, _stream()), "v3a_clip_rows")
+    return out
+
+
+def attention_f32(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, B: int, S: int, H: int, causal: bool = False,
+                  lens: Optional[torch.Tensor] = None, out_f32: bool = False, head_dim: int = 64, scale: Optional[float] = None) -> torch.Tensor:
+    """fp32 attention for short sequences (v3a_attention_f32).  q, k, v: f32 [B S, >= H 64] views sharing one row stride (columns of a fused
+    qkv buffer), head h at column 64 h.  lens: int32 [B] valid key counts.  -> pair [2, B S, H 64], or f32 [B S, H 64] with out_f32."""
+    for name, t in (("q", q), ("k", k), ("v", v)):
+        if not t.is_cuda or t.dtype != f32 or t.dim() != 2 or t.stride(1) != 1 or t.shape[0] != B * S or t.shape[1] < H * head_dim:
+            raise ValueError(f"{name} must be a device f32 [B S, >= H hd] view with unit column stride, got {t.dtype} {tuple(t.shape)}")
+    if not (q.stride(0) == k.stride(0) == v.stride(0)):
+        raise ValueError("q, k, v must share a row stride")
+    if lens is not None:
+        _dev(lens, "lens", torch.int32)
+        if lens.numel() != B:
+            raise ValueError(f"lens must be int32 [{B}]")
+    d = H * head_dim
+    out = torch.empty((B * S, d) if out_f32 else (2, B * S, d), device=q.device, dtype=f32 if out_f32 else bf16)
+    sc = head_dim ** -0.5 if scale is None else scale
+    L.check(L.load().v3a_attention_f32(_ptr(q), _ptr(k), _ptr(v), q.stride(0), None if out_f32 else _ptr(out[0]),
+                                       None if out_f32 else _ptr(out[1]), _ptr(out) if out_f32 else None, d, _ptr(lens), B, S, H, head_dim,
+                                       sc, int(causal), _stream()), "v3a_attention_f32")
+    return out
+
+
+def clip_score(image_emb: torch.Tensor, text_emb: torch.Tensor):
+    """-> (scores f64 [F] = max(100 cos(image_emb[f], text_emb), 0), their mean f64 [1]); fp64 on the device, fixed summation order"""
+    _dev(image_emb, "image_emb", f32, 2)
+    _dev(text_emb, "text_emb", f32)
+    F, D = image_emb.shape
+    if text_emb.numel() != D:
+        raise ValueError(f"text_emb must hold {D} values, got {tuple(text_emb.shape)}")
+    scores = torch.empty(F, device=image_emb.device, dtype=torch.float64)
+    mean = torch.empty(1, device=image_emb.device, dtype=torch.float64)
+    L.check(L.load().v3a_clip_score(_ptr(image_emb), _ptr(text_emb), F, D, _ptr(scores), _ptr(mean), _stream()), "v3a_clip_score")
+    return scores, mean
