@@ -23,7 +23,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 25) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 26) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -611,6 +611,53 @@ int v3a_clip_rows(const float* src, int src_rows, const int* ids, const float* c
 int v3a_attention_f32(const float* q, const float* k, const float* v, int ld, void* o_hi, void* o_lo, float* o_f32, int ldo,
                       const int* lens, int B, int S, int H, int hd, float scale, int causal, void* stream);
 int v3a_clip_score(const float* image_emb, const float* text_emb, int F, int D, double* scores, double* mean, void* stream);
+
+/* ---- Post-optimisation of predicted Gaussians (third_party_model/anysplat/src/post_opt/simple_trainer.py; vist3a_amd/post_opt).
+ *
+ * Photometric loss (csrc/ssim_loss.hip): pred, target f32 [N,H,W,C] (the rasteriser's layout), C <= 4, H, W >= 11 (smaller:
+ * V3A_ERR_SHAPE; the reference would silently skip the smoothing).  out[0] = loss = (1 - ssim_lambda) l1 + ssim_lambda (1 - ssim),
+ * out[1] = l1 = mean |pred - target|, out[2] = ssim = mean over the (H-10) x (W-10) valid map, all channels and images, of the
+ * reference's loss_ssim.py::ssim(data_range=1.0) (11-tap Gaussian, sigma 1.5, population variances, C1 = 1e-4, C2 = 9e-4).  fp64
+ * arithmetic on the fp32 inputs; fp64 partials reduced in a fixed order: bit-identical run to run; identical images give exactly
+ * (0, 0, 1).  Forward = two launches; with planes != NULL it also stores the three derivative planes [3][N][C][H-10][W-10] (fp64)
+ * that the backward reads.  Backward = one launch, gather form, no atomics: d_pred (f32, shape of pred, every element written
+ * once) from d_out[3] = the gradients of (loss, l1, ssim) on the device; sign(0) = 0 in the L1 part. */
+typedef struct {
+  const float* pred; const float* target;
+  int N, H, W, C;
+  double ssim_lambda;
+  double* out;                               /* [3]: loss, l1, ssim (forward only) */
+  void* workspace; long workspace_bytes;     /* v3a_photometric_loss_workspace_bytes(N, H, W, C) (forward only) */
+  double* planes; long planes_bytes;         /* v3a_photometric_loss_planes_bytes(N, H, W, C); NULL in a forward without gradient */
+} v3a_photometric_loss_args;
+long v3a_photometric_loss_workspace_bytes(int N, int H, int W, int C);   /* V3A_ERR_SHAPE for a shape the loss rejects */
+long v3a_photometric_loss_planes_bytes(int N, int H, int W, int C);
+int v3a_photometric_loss_forward(const v3a_photometric_loss_args* a, void* stream);
+int v3a_photometric_loss_backward(const v3a_photometric_loss_args* a, const double* d_out, float* d_pred, void* stream);
+
+/* Splat activation (csrc/post_opt.hip), one thread per Gaussian: log-scales [U,3], raw quaternions [U,4] (xyzw, any length),
+ * opacity logits [U] -> covariances [U,3,3] = R diag(exp(log_scale))^2 R^T with v3a_gaussian_adapter's quaternion order,
+ * normalisation and product, opacities [U] = sigmoid.  Backward: closed form from (d_covars, d_opacities); d_covars is contracted
+ * entry by entry, so the upper-triangle convention of v3a_gs_project_backward and a full symmetric gradient both give what autograd
+ * through the product gives. */
+int v3a_splat_activate(const float* log_scales, const float* quats, const float* logits, long U, float* covars, float* opacities,
+                       void* stream);
+int v3a_splat_activate_backward(const float* log_scales, const float* quats, const float* logits, const float* d_covars,
+                                const float* d_opacities, long U, float* d_log_scales, float* d_quats, float* d_logits, void* stream);
+
+/* Fused Adam (csrc/post_opt.hip), one launch per parameter tensor, in place on p, m, v (f32 [n]), reading g:
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;  p -= lr / bias_correction1 * m / (sqrt(v) / sqrt(bias_correction2) + eps)
+ * (torch.optim.Adam; the bias corrections 1 - beta^t come from the host in double).  period > 0: element e uses lr when
+ * e % period == 0 and lr2 otherwise (harmonics [U,3,K] with period K: the DC band and the rest are the reference's two optimisers);
+ * period == 0: lr everywhere.  16-byte loads and stores with a scalar tail (all scalar when a pointer is not 16-byte aligned). */
+typedef struct {
+  float* p; const float* g; float* m; float* v;
+  long n;
+  double lr, lr2;
+  int period;
+  double beta1, beta2, eps, bias_correction1, bias_correction2;
+} v3a_adam_args;
+int v3a_adam_step(const v3a_adam_args* a, void* stream);
 
 #ifdef __cplusplus
 }

@@ -63,6 +63,16 @@ def build_text_encoder(args, device):
     return make_pipeline_text_encoder(UMT5TextEncoder(UMT5Config(), sd, device=device), AutoTokenizer.from_pretrained(tk))
 
 
+def refine(gaussians, clip_cl, pose, res, steps):
+    from vist3a_amd import ops
+    from vist3a_amd.post_opt import PostOptConfig, post_optimize
+    with torch.no_grad():
+        ff = ops.bilinear_cl(clip_cl, (res, res), align_corners=False)          # what Text23DGS.generate fed the reconstruction
+        frames = ((ff[..., :3].float() + 1) / 2).clamp(0, 1).contiguous()       # [V,res,res,3] in [0,1]
+    g, _ = post_optimize(gaussians, frames, pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach(), PostOptConfig(), steps=steps)
+    return g
+
+
 def main(args):
     setup_dist()
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -94,7 +104,7 @@ def main(args):
         else:
             raise RuntimeError(f"no text encoder: {args.model_id}/text_encoder + /tokenizer are not on disk (no hub access here); pass "
                                "--text_embeds_path (precomputed UMT5 embeddings) or --synthetic_text")
-        out, _, _ = scene.generate(pe, ne, generator=gen, num_frames=args.num_frames, num_inference_steps=args.num_inference_steps,
+        out, _, clip_cl = scene.generate(pe, ne, generator=gen, num_frames=args.num_frames, num_inference_steps=args.num_inference_steps,
                                    guidance_scale=float(args.cfg_scale), height=args.resolution, width=args.resolution)
         if coop and rank != 0:
             continue
@@ -102,6 +112,8 @@ def main(args):
         os.makedirs(save, exist_ok=args.overwrite)  # the reference raises when the directory exists (inference_t23d.py:126)
         (save / "prompt.txt").write_text(prompt)
         g = out.gaussians
+        if args.post_opt_steps > 0:   # against the frames the reconstruction saw, at the predicted context poses and intrinsics
+            g = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps)
         if not args.no_video:  # orbit video through the predicted context poses (reference :144-154)
             save_interpolated_video(out.pred_context_pose["extrinsic"], out.pred_context_pose["intrinsic"], 1, args.feedforward_resolution,
                                     args.feedforward_resolution, g, str(save), stitched.stitched_3d_model.decoder)

@@ -1,0 +1,83 @@
+"""One post-optimisation step (vist3a_amd/post_opt) at the sizes of tools/raster_bwd_time.py (448^2, 1M Gaussians, SH degree 4), one camera
+per step as the loop runs it.  Prints one JSON line: milliseconds (median of --iters after --warmup) of the five parts of a step -
+activation, render forward, loss, backward (loss + render + activation), Adam over the five tensors - and the Adam launch on the
+harmonics against a `copy_` of the same bytes (28 B per element: p, m, v read and written, g read; the yardstick of tools/norm_time.py)."""
+import argparse
+import json
+import math
+import statistics
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gaussians", type=int, default=1_000_000)
+    ap.add_argument("--size", type=int, default=448)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    a = ap.parse_args()
+    from vist3a_amd import ops
+    U, W, H = a.gaussians, a.size, a.size
+    g = torch.Generator().manual_seed(9)
+    p = dict(means=torch.randn(U, 3, generator=g) * torch.tensor([2.0, 2.0, 1.0]) + torch.tensor([0.0, 0.0, 5.0]),
+             scales=torch.log(0.005 + 0.03 * torch.rand(U, 3, generator=g)), quats=torch.randn(U, 4, generator=g),
+             opacities=torch.randn(U, generator=g), sh=torch.randn(U, 3, 25, generator=g) * 0.3)
+    p = {k: t.cuda().requires_grad_(True) for k, t in p.items()}
+    m, v = {k: torch.zeros_like(t) for k, t in p.items()}, {k: torch.zeros_like(t) for k, t in p.items()}
+    yaw = -0.15
+    view = torch.eye(4)
+    view[:3, :3] = torch.tensor([[math.cos(yaw), 0, math.sin(yaw)], [0, 1, 0], [-math.sin(yaw), 0, math.cos(yaw)]])
+    view[:3, 3] = torch.tensor([0.1, -0.2, 0.3])
+    campos = torch.linalg.inv(view)[:3, 3].contiguous().cuda()[None]
+    view, K = view.cuda()[None], torch.tensor([[400.0, 0, W / 2], [0, 440.0, H / 2], [0, 0, 1.0]]).cuda()[None]
+    target, bg, ws = torch.rand(1, H, W, 3, device="cuda"), torch.zeros(3, device="cuda"), ops.GsWorkspace()
+    names = ("activation", "render_forward", "loss", "backward", "adam")
+    ms = {n: [] for n in names}
+    for it in range(a.warmup + a.iters):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        e[0].record()
+        cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        e[1].record()
+        col, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, view, campos, K, W, H, background=bg, clamp_rgb=True, workspace=ws)
+        e[2].record()
+        loss, _, _ = ops.photometric_loss(col, target, 0.2)
+        e[3].record()
+        grads = torch.autograd.grad(loss, list(p.values()))
+        e[4].record()
+        with torch.no_grad():
+            for (k, t), gr in zip(p.items(), grads):
+                ops.adam_step(t, gr, m[k], v[k], lr=1e-3, step=it + 1, eps=1e-15, lr2=5e-5 if k == "sh" else None, period=25 if k == "sh" else 0)
+        e[5].record()
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            for i, n in enumerate(names):
+                ms[n].append(e[i].elapsed_time(e[i + 1]))
+    med = {n: statistics.median(x) for n, x in ms.items()}
+    # the Adam launch on the harmonics alone against a copy of the same bytes
+    sh, gr = p["sh"].detach(), torch.randn(U, 3, 25, device="cuda")
+    src, dst = torch.empty(sh.numel() * 7 // 2, device="cuda"), torch.empty(sh.numel() * 7 // 2, device="cuda")   # 14 B read + 14 B written per element
+    ta, tc = [], []
+    for it in range(a.warmup + a.iters):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        ops.adam_step(sh, gr, m["sh"], v["sh"], lr=1e-3, lr2=5e-5, period=25, step=it + 1, eps=1e-15)
+        e[1].record()
+        dst.copy_(src)
+        e[2].record()
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            ta.append(e[0].elapsed_time(e[1]))
+            tc.append(e[1].elapsed_time(e[2]))
+    nbytes = sh.numel() * 28
+    a_ms, c_ms = statistics.median(ta), statistics.median(tc)
+    print(json.dumps(dict(gaussians=U, size=W, step_ms=round(sum(med.values()), 3), **{n + "_ms": round(x, 3) for n, x in med.items()},
+                          adam_sh_elements=sh.numel(), adam_sh_ms=round(a_ms, 3), adam_sh_GBps=round(nbytes / a_ms / 1e6, 1),
+                          copy_same_bytes_ms=round(c_ms, 3), copy_GBps=round(nbytes / c_ms / 1e6, 1), adam_over_copy=round(a_ms / c_ms, 2))))
+
+
+if __name__ == "__main__":
+    main()

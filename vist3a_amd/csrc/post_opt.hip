@@ -1,0 +1,198 @@
+// Post-optimisation of predicted Gaussians (third_party_model/anysplat/src/post_opt/simple_trainer.py): the two elementwise
+// passes around the rasteriser and the photometric loss.
+//
+//   splat activation   (log-scales, raw quaternions xyzw, opacity logits) -> (covariances, opacities), forward and backward.
+//                      What gsplat does inside its rasterisation call from exp(scales), quats, sigmoid(opacities)
+//                      (simple_trainer.py:607-634); here the covariance is explicit because v3a_gs_project takes one.  Quaternion
+//                      order, internal normalisation and the product are those of gaussian_adapter_kernel (elementwise.hip).
+//   fused Adam         torch.optim.Adam's update on one parameter tensor per launch (simple_trainer.py:442-460: one optimiser per
+//                      tensor, eps 1e-15), in place.
+#include "common.h"
+#include "../../include/vist3a_hip.h"
+
+namespace {
+
+// rotation of a quaternion (i, j, k, r), normalised the way the adapter normalises it
+__device__ __forceinline__ void quat_R(const float* qin, float* R) {
+  float q[4], n2 = 0.f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { q[e] = qin[e]; n2 += q[e] * q[e]; }
+  const float inv = 1.f / (sqrtf(n2) + 1e-8f);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) q[e] *= inv;
+  const float i = q[0], j = q[1], k = q[2], r = q[3];
+  const float two_s = 2.0f / (i * i + j * j + k * k + r * r);
+  R[0] = 1 - two_s * (j * j + k * k); R[1] = two_s * (i * j - k * r);     R[2] = two_s * (i * k + j * r);
+  R[3] = two_s * (i * j + k * r);     R[4] = 1 - two_s * (i * i + k * k); R[5] = two_s * (j * k - i * r);
+  R[6] = two_s * (i * k - j * r);     R[7] = two_s * (j * k + i * r);     R[8] = 1 - two_s * (i * i + j * j);
+}
+
+// One thread per Gaussian: 8 floats in, 10 out; rows of adjacent lanes are adjacent in memory.
+__global__ void __launch_bounds__(256) splat_activate_kernel(const float* __restrict__ log_scales, const float* __restrict__ quats,
+                                                             const float* __restrict__ logits, long U, float* __restrict__ cov,
+                                                             float* __restrict__ opac) {
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= U) return;
+  float s[3], q[4], R[9];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) s[e] = expf(log_scales[u * 3 + e]);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) q[e] = quats[u * 4 + e];
+  quat_R(q, R);
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      float acc = 0.f;
+#pragma unroll
+      for (int m = 0; m < 3; ++m) acc += (R[a * 3 + m] * s[m]) * s[m] * R[b * 3 + m];
+      cov[u * 9 + a * 3 + b] = acc;
+    }
+  opac[u] = 1.f / (1.f + expf(-logits[u]));
+}
+
+// Closed form.  With G = d_covars (any 3 x 3: v3a_gs_project_backward fills the upper triangle only and lets an off-diagonal entry
+// carry both symmetric positions; autograd through C = R D R^T contracts G with dC entry by entry, and so does this):
+//   dD_m = r_m^T G r_m (r_m = column m of R),  d log s_m = 2 s_m^2 dD_m,  dR = (G + G^T) R D,
+// and R(q) = I + t M(q), t = 2 / |q|^2 (the normalisation cancels: R is invariant to the quaternion's length), so
+//   dq_e = t sum_ab dR_ab dM_ab/dq_e - (2 t q_e / |q|^2) sum_ab dR_ab M_ab.
+__global__ void __launch_bounds__(256) splat_activate_bwd_kernel(const float* __restrict__ log_scales, const float* __restrict__ quats,
+                                                                 const float* __restrict__ logits, const float* __restrict__ d_cov,
+                                                                 const float* __restrict__ d_opac, long U,
+                                                                 float* __restrict__ d_log_scales, float* __restrict__ d_quats,
+                                                                 float* __restrict__ d_logits) {
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= U) return;
+  float s2[3], q[4], R[9], G[9];
+#pragma unroll
+  for (int e = 0; e < 3; ++e) { const float s = expf(log_scales[u * 3 + e]); s2[e] = s * s; }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) q[e] = quats[u * 4 + e];
+#pragma unroll
+  for (int e = 0; e < 9; ++e) G[e] = d_cov[u * 9 + e];
+  quat_R(q, R);
+  float g[9];   // dR
+#pragma unroll
+  for (int m = 0; m < 3; ++m) {
+    float gr[3], dD = 0.f;   // (G + G^T) r_m
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      float acc = 0.f, accG = 0.f;
+#pragma unroll
+      for (int b = 0; b < 3; ++b) {
+        acc += (G[a * 3 + b] + G[b * 3 + a]) * R[b * 3 + m];
+        accG += G[a * 3 + b] * R[b * 3 + m];
+      }
+      gr[a] = acc;
+      dD += R[a * 3 + m] * accG;
+    }
+    d_log_scales[u * 3 + m] = 2.f * s2[m] * dD;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) g[a * 3 + m] = gr[a] * s2[m];
+  }
+  const float i = q[0], j = q[1], k = q[2], r = q[3];
+  const float n2 = i * i + j * j + k * k + r * r;
+  const float t = 2.f / n2;
+  const float S = g[0] * -(j * j + k * k) + g[1] * (i * j - k * r) + g[2] * (i * k + j * r)
+                + g[3] * (i * j + k * r) + g[4] * -(i * i + k * k) + g[5] * (j * k - i * r)
+                + g[6] * (i * k - j * r) + g[7] * (j * k + i * r) + g[8] * -(i * i + j * j);
+  const float di = j * (g[1] + g[3]) + k * (g[2] + g[6]) + r * (g[7] - g[5]) - 2.f * i * (g[4] + g[8]);
+  const float dj = i * (g[1] + g[3]) + k * (g[5] + g[7]) + r * (g[2] - g[6]) - 2.f * j * (g[0] + g[8]);
+  const float dk = i * (g[2] + g[6]) + j * (g[5] + g[7]) + r * (g[3] - g[1]) - 2.f * k * (g[0] + g[4]);
+  const float dr = i * (g[7] - g[5]) + j * (g[2] - g[6]) + k * (g[3] - g[1]);
+  const float c = 2.f * t / n2 * S;
+  d_quats[u * 4 + 0] = t * di - c * i;
+  d_quats[u * 4 + 1] = t * dj - c * j;
+  d_quats[u * 4 + 2] = t * dk - c * k;
+  d_quats[u * 4 + 3] = t * dr - c * r;
+  const float o = 1.f / (1.f + expf(-logits[u]));
+  d_logits[u] = d_opac[u] * o * (1.f - o);
+}
+
+struct AdamP {
+  float* p; const float* g; float* m; float* v;
+  long n, nvec;
+  int period;              // > 0: element e uses step2 unless e % period == 0
+  double b1, b2, step1, step2;
+  float inv_sqrt_bc2, eps;
+};
+
+// The moments and the parameter are advanced in fp64 and rounded once on store (they are fp32 in memory): the kernel is bound by its
+// 28 bytes per element, and m = b1 m + (1 - b1) g cancels when the gradient changes sign, where fp32 arithmetic loses digits.
+__device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, double step, const AdamP& a) {
+  const float mn = (float)(a.b1 * (double)m + (1.0 - a.b1) * (double)g);
+  const float vn = (float)(a.b2 * (double)v + (1.0 - a.b2) * ((double)g * (double)g));
+  const float upd = mn / (sqrtf(vn) * a.inv_sqrt_bc2 + a.eps);
+  m = mn;
+  v = vn;
+  p = (float)((double)p - step * (double)upd);
+}
+
+__global__ void __launch_bounds__(256) adam_kernel(const AdamP a) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t < a.nvec) {   // 16-byte loads and stores
+    float4 p = ((const float4*)a.p)[t], m = ((const float4*)a.m)[t], v = ((const float4*)a.v)[t];
+    const float4 g = ((const float4*)a.g)[t];
+    double st[4];
+    const unsigned r0 = a.period > 0 ? (unsigned)((t * 4) % a.period) : 0u;   // one 64-bit remainder per lane, the rest in 32 bits
+#pragma unroll
+    for (int e = 0; e < 4; ++e) st[e] = (a.period > 0 && (r0 + e) % (unsigned)a.period != 0) ? a.step2 : a.step1;
+    adam_one(p.x, g.x, m.x, v.x, st[0], a);
+    adam_one(p.y, g.y, m.y, v.y, st[1], a);
+    adam_one(p.z, g.z, m.z, v.z, st[2], a);
+    adam_one(p.w, g.w, m.w, v.w, st[3], a);
+    ((float4*)a.p)[t] = p;
+    ((float4*)a.m)[t] = m;
+    ((float4*)a.v)[t] = v;
+  } else {            // scalar tail (and the whole tensor when a pointer is not 16-byte aligned)
+    const long e = a.nvec * 4 + (t - a.nvec);
+    if (e >= a.n) return;
+    float p = a.p[e], m = a.m[e], v = a.v[e];
+    adam_one(p, a.g[e], m, v, (a.period > 0 && e % a.period != 0) ? a.step2 : a.step1, a);
+    a.p[e] = p;
+    a.m[e] = m;
+    a.v[e] = v;
+  }
+}
+
+}  // namespace
+
+extern "C" int v3a_splat_activate(const float* log_scales, const float* quats, const float* logits, long U, float* covars,
+                                  float* opacities, void* stream) {
+  if (!log_scales || !quats || !logits || !covars || !opacities) return V3A_ERR_ARG;
+  if (U < 1 || U > 0x7fffffffL * 256) return V3A_ERR_SHAPE;
+  hipLaunchKernelGGL(splat_activate_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, (hipStream_t)stream, log_scales, quats, logits,
+                     U, covars, opacities);
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}
+
+extern "C" int v3a_splat_activate_backward(const float* log_scales, const float* quats, const float* logits, const float* d_covars,
+                                           const float* d_opacities, long U, float* d_log_scales, float* d_quats, float* d_logits,
+                                           void* stream) {
+  if (!log_scales || !quats || !logits || !d_covars || !d_opacities || !d_log_scales || !d_quats || !d_logits) return V3A_ERR_ARG;
+  if (U < 1 || U > 0x7fffffffL * 256) return V3A_ERR_SHAPE;
+  hipLaunchKernelGGL(splat_activate_bwd_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, (hipStream_t)stream, log_scales, quats,
+                     logits, d_covars, d_opacities, U, d_log_scales, d_quats, d_logits);
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}
+
+extern "C" int v3a_adam_step(const v3a_adam_args* a, void* stream) {
+  if (!a || !a->p || !a->g || !a->m || !a->v) return V3A_ERR_ARG;
+  if (a->n < 1 || a->period < 0 || !(a->bias_correction1 > 0.0) || !(a->bias_correction2 > 0.0)) return V3A_ERR_SHAPE;
+  AdamP k;
+  k.p = a->p; k.g = a->g; k.m = a->m; k.v = a->v;
+  k.n = a->n;
+  const uintptr_t al = (uintptr_t)a->p | (uintptr_t)a->g | (uintptr_t)a->m | (uintptr_t)a->v;
+  k.nvec = (al & 15) ? 0 : a->n / 4;
+  k.period = a->period;
+  k.b1 = a->beta1;
+  k.b2 = a->beta2;
+  k.step1 = a->lr / a->bias_correction1;
+  k.step2 = a->lr2 / a->bias_correction1;
+  k.inv_sqrt_bc2 = (float)(1.0 / sqrt(a->bias_correction2));
+  k.eps = (float)a->eps;
+  const long threads = k.nvec + (a->n - 4 * k.nvec);
+  if ((threads + 255) / 256 > 0x7fffffffL) return V3A_ERR_SHAPE;
+  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}

@@ -227,6 +227,27 @@ class ImageMetricsArgs(C.Structure):
     ]
 
 
+class PhotometricLossArgs(C.Structure):
+    _fields_ = [
+        ("pred", C.c_void_p), ("target", C.c_void_p),
+        ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
+        ("ssim_lambda", C.c_double),
+        ("out", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+        ("planes", C.c_void_p), ("planes_bytes", C.c_long),
+    ]
+
+
+class AdamArgs(C.Structure):
+    _fields_ = [
+        ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
+        ("n", C.c_long),
+        ("lr", C.c_double), ("lr2", C.c_double), ("period", C.c_int),
+        ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+        ("bias_correction1", C.c_double), ("bias_correction2", C.c_double),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/vist3a_hip.h declares must be listed here
 SYMBOLS = {
     "v3a_abi_version": (C.c_int, []),
@@ -294,10 +315,17 @@ SYMBOLS = {
     "v3a_attention_f32": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4
                           + [C.c_float, C.c_int, C.c_void_p]),
     "v3a_clip_score": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v3a_photometric_loss_workspace_bytes": (C.c_long, [C.c_int] * 4),
+    "v3a_photometric_loss_planes_bytes": (C.c_long, [C.c_int] * 4),
+    "v3a_photometric_loss_forward": (C.c_int, [C.POINTER(PhotometricLossArgs), C.c_void_p]),
+    "v3a_photometric_loss_backward": (C.c_int, [C.POINTER(PhotometricLossArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v3a_splat_activate": (C.c_int, [C.c_void_p] * 3 + [C.c_long] + [C.c_void_p] * 3),
+    "v3a_splat_activate_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),
+    "v3a_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 25   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 26   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

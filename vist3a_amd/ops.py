@@ -1373,3 +1373,110 @@ def clip_score(image_emb: torch.Tensor, text_emb: torch.Tensor):
     mean = torch.empty(1, device=image_emb.device, dtype=torch.float64)
     L.check(L.load().v3a_clip_score(_ptr(image_emb), _ptr(text_emb), F, D, _ptr(scores), _ptr(mean), _stream()), "v3a_clip_score")
     return scores, mean
+
+
+# ------------------------------------------------------------------------------------------------ post-optimisation (csrc/ssim_loss.hip, csrc/post_opt.hip)
+def _f32_dev(t: torch.Tensor, name: str, shape=None) -> None:
+    if not t.is_cuda or t.dtype != f32 or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 device tensor, got {t.dtype} on {t.device}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+
+
+class _PhotometricLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, ssim_lambda):
+        N, H, W, Cc = pred.shape
+        lib = L.load()
+        need = lib.v3a_photometric_loss_workspace_bytes(N, H, W, Cc)
+        if need < 0:
+            L.check(int(need), f"v3a_photometric_loss_workspace_bytes (shape {tuple(pred.shape)}; H, W >= 11 and C <= 4 required)")
+        dev = pred.device
+        ws = torch.empty(int(need), device=dev, dtype=torch.uint8)
+        planes = None
+        if ctx.needs_input_grad[0]:
+            planes = torch.empty(int(lib.v3a_photometric_loss_planes_bytes(N, H, W, Cc)) // 8, device=dev, dtype=torch.float64)
+        out = torch.empty(3, device=dev, dtype=torch.float64)
+        args = L.PhotometricLossArgs(_ptr(pred), _ptr(target), N, H, W, Cc, float(ssim_lambda), _ptr(out), _ptr(ws), ws.numel(),
+                                     _ptr(planes), planes.numel() * 8 if planes is not None else 0)
+        L.check(lib.v3a_photometric_loss_forward(C.byref(args), _stream()), "v3a_photometric_loss_forward")
+        if planes is not None:
+            ctx.save_for_backward(pred, target, planes)
+        ctx.ssim_lambda = float(ssim_lambda)
+        return out[0], out[1], out[2]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss, d_l1, d_ssim):
+        pred, target, planes = ctx.saved_tensors
+        N, H, W, Cc = pred.shape
+        z = torch.zeros((), device=pred.device, dtype=torch.float64)
+        d_out = torch.stack([z if g is None else g.to(torch.float64).reshape(()) for g in (d_loss, d_l1, d_ssim)])
+        d_pred = torch.empty_like(pred)
+        args = L.PhotometricLossArgs(_ptr(pred), _ptr(target), N, H, W, Cc, ctx.ssim_lambda, None, None, 0, _ptr(planes), planes.numel() * 8)
+        L.check(L.load().v3a_photometric_loss_backward(C.byref(args), _ptr(d_out), _ptr(d_pred), _stream()), "v3a_photometric_loss_backward")
+        return d_pred, None, None
+
+
+def photometric_loss(pred: torch.Tensor, target: torch.Tensor, ssim_lambda: float = 0.2):
+    """(1 - ssim_lambda) * L1 + ssim_lambda * (1 - SSIM) of f32 images [N,H,W,C] (C <= 4, H, W >= 11; the layout gs_render emits),
+    SSIM as the reference's loss_ssim.py::ssim(data_range=1.0) on the valid map = fused_ssim(padding="valid") (csrc/ssim_loss.hip).
+    -> (loss, l1, ssim): float64 scalars on the device, differentiable with respect to `pred` (HIP backward, first order only).
+    `target` is a constant: one that requires grad is refused."""
+    if target.requires_grad:
+        raise NotImplementedError("photometric_loss: no gradient for target (it is a constant of the loss); detach it")
+    if pred.dim() != 4:
+        raise ValueError(f"photometric_loss: pred must be [N,H,W,C], got {tuple(pred.shape)}")
+    _f32_dev(pred, "pred")
+    _f32_dev(target, "target", pred.shape)
+    return _PhotometricLoss.apply(pred, target, float(ssim_lambda))
+
+
+class _SplatActivate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, log_scales, quats, logits):
+        U = logits.shape[0]
+        cov = torch.empty(U, 3, 3, device=logits.device, dtype=f32)
+        op = torch.empty(U, device=logits.device, dtype=f32)
+        L.check(L.load().v3a_splat_activate(_ptr(log_scales), _ptr(quats), _ptr(logits), U, _ptr(cov), _ptr(op), _stream()), "v3a_splat_activate")
+        ctx.save_for_backward(log_scales, quats, logits)
+        return cov, op
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_cov, d_op):
+        log_scales, quats, logits = ctx.saved_tensors
+        U = logits.shape[0]
+        d_cov = torch.zeros(U, 3, 3, device=logits.device, dtype=f32) if d_cov is None else d_cov.float().contiguous()
+        d_op = torch.zeros(U, device=logits.device, dtype=f32) if d_op is None else d_op.float().contiguous()
+        d_ls, d_q, d_lg = torch.empty_like(log_scales), torch.empty_like(quats), torch.empty_like(logits)
+        L.check(L.load().v3a_splat_activate_backward(_ptr(log_scales), _ptr(quats), _ptr(logits), _ptr(d_cov), _ptr(d_op), U, _ptr(d_ls),
+                                                     _ptr(d_q), _ptr(d_lg), _stream()), "v3a_splat_activate_backward")
+        return d_ls, d_q, d_lg
+
+
+def splat_activate(log_scales: torch.Tensor, quats: torch.Tensor, logits: torch.Tensor):
+    """(log-scales [U,3], raw quaternions [U,4] xyzw, opacity logits [U]) -> (covariances [U,3,3], opacities [U]), the inverse of
+    (log g.scales, g.rotations, logit g.opacities) of gaussian_adapter's output; differentiable (closed-form HIP backward)."""
+    U = logits.shape[0]
+    if U < 1:
+        raise ValueError("splat_activate: no Gaussians")
+    _f32_dev(log_scales, "log_scales", (U, 3))
+    _f32_dev(quats, "quats", (U, 4))
+    _f32_dev(logits, "logits", (U,))
+    return _SplatActivate.apply(log_scales, quats, logits)
+
+
+def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, *, lr: float, step: int, betas=(0.9, 0.999),
+              eps: float = 1e-8, lr2: Optional[float] = None, period: int = 0) -> None:
+    """One torch.optim.Adam update of p (f32, any shape), in place on p, m, v, reading the gradient g; `step` counts from 1 and
+    sets the bias corrections (computed here in double).  period > 0 with lr2: flat element e uses lr where e % period == 0 and lr2
+    elsewhere - the harmonics [U,3,K] with period K are the reference's sh0 / shN optimisers in one launch."""
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        _f32_dev(t, name, p.shape)
+    if step < 1:
+        raise ValueError("adam_step: step counts from 1")
+    b1, b2 = float(betas[0]), float(betas[1])
+    a = L.AdamArgs(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(lr if lr2 is None else lr2), int(period), b1, b2, float(eps),
+                   1.0 - b1 ** step, 1.0 - b2 ** step)
+    L.check(L.load().v3a_adam_step(C.byref(a), _stream()), "v3a_adam_step")

@@ -1,0 +1,160 @@
+"""The reference's post-optimisation loop (third_party_model/anysplat/src/post_opt/simple_trainer.py) on this package's kernels.
+
+`create_splats` is create_splats_with_optimizers (:402-462): a `Gaussians` object becomes the parameters means, log-scales,
+quaternions, opacity logits and harmonics, each with its Adam moments.  `post_optimize` is train() (:804-1152) with the features the
+reference switches off, or that need what this package does not have, left out (DESIGN.md section 7f lists them): one view per step,
+loss = 0.8 L1 + 0.2 (1 - SSIM) (:938-942), one Adam (eps 1e-15) per tensor, the means' rate decaying to 1 % over max_steps, no
+densification (:389-392).  Every step is ops.splat_activate -> ops.gs_render -> ops.photometric_loss -> backward -> ops.adam_step per
+trained tensor: HIP kernels throughout, torch only carries the autograd graph.  Nothing in the loop reads a value back to the host
+(apart from the rasteriser's own intersection count); the per-step loss, L1 and SSIM stay in a device tensor.
+
+The harmonics stay ONE [U,3,K] tensor: the reference's sh0 / shN optimisers (rates lr_sh and lr_sh / 20) are one ops.adam_step with
+a period of K, which is the same arithmetic because Adam is elementwise."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from math import isqrt
+from typing import Optional, Tuple
+
+import torch
+
+from .. import ops
+from ..models.types import Gaussians
+
+PARAM_NAMES = ("means", "scales", "quats", "opacities", "sh")   # "sh" = the reference's sh0 and shN
+
+
+@dataclass
+class PostOptConfig:
+    # the reference's Config fields and defaults (simple_trainer.py:52-180, 442-460)
+    max_steps: int = 3000
+    ssim_lambda: float = 0.2
+    lr_means: float = 1.6e-4
+    lr_scales: float = 5e-3
+    lr_quats: float = 1e-3
+    lr_opacities: float = 5e-2
+    lr_sh: float = 2.5e-3            # sh0; shN trains at lr_sh / 20
+    betas: Tuple[float, float] = (0.9, 0.999)
+    eps: float = 1e-15
+    min_opacity: float = 0.01        # Gaussians at or below it are dropped at creation (:427)
+    # ours
+    params: Tuple[str, ...] = ("means", "scales", "quats", "opacities", "sh0", "shN")
+    seed: int = 0
+
+    def trained(self) -> Tuple[str, ...]:
+        names = set(self.params)
+        bad = names - {"means", "scales", "quats", "opacities", "sh0", "shN", "sh"}
+        if bad:
+            raise ValueError(f"PostOptConfig.params: unknown parameter names {sorted(bad)}")
+        if ("sh0" in names) != ("shN" in names):
+            raise ValueError("PostOptConfig.params: sh0 and shN are one tensor here and train together (name both, or 'sh')")
+        if names & {"sh0", "shN"}:
+            names = (names - {"sh0", "shN"}) | {"sh"}
+        return tuple(n for n in PARAM_NAMES if n in names)
+
+
+def view_order(n_views: int, steps: int, seed: int) -> list:
+    """The view of every step: one permutation of the views per epoch from a CPU generator seeded with `seed`."""
+    g = torch.Generator().manual_seed(int(seed))
+    out = []
+    while len(out) < steps:
+        out += torch.randperm(n_views, generator=g).tolist()
+    return out[:steps]
+
+
+def _single(gaussians: Gaussians) -> None:
+    if gaussians.means.dim() != 3 or gaussians.means.shape[0] != 1:
+        raise ValueError(f"post-optimisation takes one scene (batch dimension 1), got means of shape {tuple(gaussians.means.shape)}")
+
+
+def create_splats(gaussians: Gaussians, cfg: PostOptConfig) -> dict:
+    """-> {"params": {name: f32 tensor}, "m": {...}, "v": {...}, "step": 0, "keep": bool [U] (the rows kept)}.  scales are stored as
+    logs, opacities as logits (clamped to 1 - 1e-6 so that the logit is finite), quaternions as they come (xyzw, as `Gaussians` keeps them)."""
+    _single(gaussians)
+    if not gaussians.means.is_cuda:
+        raise ValueError("post-optimisation runs on the device (the HIP path has no CPU fallback)")
+    with torch.no_grad():
+        op = gaussians.opacities[0].reshape(-1).float()
+        keep = op > cfg.min_opacity
+        sel = lambda t: t[0].float()[keep].contiguous()
+        p = dict(means=sel(gaussians.means), scales=torch.log(sel(gaussians.scales)), quats=sel(gaussians.rotations),
+                 opacities=torch.logit(op[keep].clamp(max=1 - 1e-6)).contiguous(), sh=sel(gaussians.harmonics))
+    if p["means"].shape[0] == 0:
+        raise ValueError(f"no Gaussian has an opacity above min_opacity = {cfg.min_opacity}")
+    return dict(params=p, m={k: torch.zeros_like(t) for k, t in p.items()}, v={k: torch.zeros_like(t) for k, t in p.items()}, step=0, keep=keep)
+
+
+def _cameras(extrinsics, intrinsics, W, H, dev):
+    # tiny per-camera matrices on the host, exactly as DecoderSplattingCUDA derives them
+    w2c = torch.linalg.inv(extrinsics.float().cpu())
+    c2w = torch.linalg.inv(w2c)
+    K = intrinsics.float().cpu().clone()
+    K[:, 0] = K[:, 0] * W
+    K[:, 1] = K[:, 1] * H
+    return w2c.contiguous().to(dev), c2w[:, :3, 3].contiguous().to(dev), K.contiguous().to(dev)
+
+
+def splats_to_gaussians(splats: dict) -> Gaussians:
+    """All six fields consistent: scales = exp, opacities = sigmoid, covariances rebuilt from them, rotations normalised."""
+    p = splats["params"]
+    with torch.no_grad():
+        cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        return Gaussians(means=p["means"].detach().clone()[None], covariances=cov[None], harmonics=p["sh"].detach().clone()[None],
+                         opacities=op[None], scales=torch.exp(p["scales"])[None],
+                         rotations=torch.nn.functional.normalize(p["quats"], dim=-1)[None])
+
+
+def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.Tensor, intrinsics: torch.Tensor,
+                  cfg: Optional[PostOptConfig] = None, steps: Optional[int] = None, splats: Optional[dict] = None):
+    """Refine one scene's Gaussians against `images` (f32 [V,H,W,3] in [0,1], on the device) seen from `extrinsics` (camera-to-world
+    [V,4,4]) with `intrinsics` (normalised [V,3,3]) - the decoder's conventions.  `steps` (default cfg.max_steps) steps of one view
+    each; the means' learning-rate schedule always spans cfg.max_steps.  -> (Gaussians, log): the refined scene (rows at or below
+    cfg.min_opacity dropped) and a float64 device tensor [steps,3] of per-step (loss, l1, ssim)."""
+    cfg = cfg or PostOptConfig()
+    _single(gaussians)
+    for t, n in ((extrinsics, "extrinsics"), (intrinsics, "intrinsics")):
+        if t.requires_grad:
+            raise NotImplementedError(f"post_optimize: no gradient for {n} (cameras are constants; pose optimisation is not implemented)")
+    if images.dim() != 4 or images.shape[-1] != 3 or images.dtype != torch.float32:
+        raise ValueError(f"images must be float32 [V,H,W,3], got {images.dtype} {tuple(images.shape)}")
+    V, H, W, _ = images.shape
+    if tuple(extrinsics.shape) != (V, 4, 4) or tuple(intrinsics.shape) != (V, 3, 3):
+        raise ValueError(f"extrinsics [V,4,4] and intrinsics [V,3,3] must match the {V} images, got {tuple(extrinsics.shape)} and "
+                         f"{tuple(intrinsics.shape)}")
+    if not images.is_cuda:
+        raise ValueError("images must be on the device (the HIP path has no CPU fallback)")
+    steps = cfg.max_steps if steps is None else int(steps)
+    trained = cfg.trained()
+    splats = splats if splats is not None else create_splats(gaussians, cfg)
+    p, m, v = splats["params"], splats["m"], splats["v"]
+    dev = p["means"].device
+    Ksh = p["sh"].shape[-1]
+    sh_degree = isqrt(Ksh) - 1
+    view, campos, Kpix = _cameras(extrinsics, intrinsics, W, H, dev)
+    images = images.contiguous()
+    background = torch.zeros(3, device=dev, dtype=torch.float32)
+    log = torch.zeros(steps, 3, device=dev, dtype=torch.float64)
+    lrs = dict(means=cfg.lr_means, scales=cfg.lr_scales, quats=cfg.lr_quats, opacities=cfg.lr_opacities, sh=cfg.lr_sh)
+    decay = 0.01 ** (1.0 / cfg.max_steps)
+    ws = ops.GsWorkspace()
+    leaves = [p[n].requires_grad_(True) for n in trained]
+    try:
+        for i, j in enumerate(view_order(V, steps, cfg.seed)):
+            cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+            color, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
+                                        sh_degree=sh_degree, sh_layout=1, background=background, clamp_rgb=True, workspace=ws)
+            loss, l1, ssim = ops.photometric_loss(color, images[j:j + 1], cfg.ssim_lambda)
+            grads = torch.autograd.grad(loss, leaves)
+            log[i].copy_(torch.stack([loss.detach(), l1.detach(), ssim.detach()]))
+            t = splats["step"] + 1
+            with torch.no_grad():
+                for n, g in zip(trained, grads):
+                    lr = lrs[n] * (decay ** (t - 1) if n == "means" else 1.0)
+                    sh = n == "sh"
+                    ops.adam_step(p[n], g.contiguous(), m[n], v[n], lr=lr, step=t, betas=cfg.betas, eps=cfg.eps,
+                                  lr2=lr / 20 if sh else None, period=Ksh if sh and Ksh > 1 else 0)
+            splats["step"] = t
+    finally:
+        for n in trained:
+            p[n].requires_grad_(False)
+    return splats_to_gaussians(splats), log

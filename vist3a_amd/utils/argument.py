@@ -40,6 +40,9 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
                    help="all ranks cooperate on each prompt (CFG-parallel x sequence-parallel DiT over RCCL) instead of striding prompts")
     g.add_argument("--no_video", action="store_true", help="skip the interpolated orbit render (gs.avi / depth.avi)")
     g.add_argument("--overwrite", action="store_true", help="reuse an existing output directory (the reference raises)")
+    g.add_argument("--post_opt_steps", type=int, default=0,
+                   help="refine the predicted Gaussians for N steps against the frames the reconstruction was fed (AnySplat's post-optimisation, "
+                        "vist3a_amd/post_opt) before gaussians.ply and the videos are written; 0 = off")
     return p
 
 
