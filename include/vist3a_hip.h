@@ -23,7 +23,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 26) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 27) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -634,6 +634,29 @@ long v3a_photometric_loss_workspace_bytes(int N, int H, int W, int C);   /* V3A_
 long v3a_photometric_loss_planes_bytes(int N, int H, int W, int C);
 int v3a_photometric_loss_forward(const v3a_photometric_loss_args* a, void* stream);
 int v3a_photometric_loss_backward(const v3a_photometric_loss_args* a, const double* d_out, float* d_pred, void* stream);
+
+/* Depth term (csrc/depth_loss.hip; simple_trainer.py:943-961 with `points` = the integer coordinates of the used pixels): depth, alpha
+ * f32 [C,H,W] as v3a_gs_rasterize emits them (depth = the alpha-weighted z), depth_gt f32 [C,H,W], mask uint8 [C,H,W] (nonzero = use
+ * the pixel) or NULL (all), C H W < 2^31.  Per pixel in fp64: E = depth / max(alpha, 1e-10) (gsplat's expected depth, never
+ * materialised), disp = E > 0 ? 1 / E : 0, used = mask && depth_gt > 0 && isfinite(depth_gt), term = |disp - 1 / depth_gt|;
+ * out[0] = loss = scale * sum(term) / M, out[1] = M = the number of used pixels of all C cameras.  Deviations from the reference: a
+ * pixel whose target is not a positive finite number is skipped (the reference divides by it), and M == 0 gives loss 0 and zero
+ * gradients (the reference's empty mean is NaN).  Forward = two launches, fp64 partials and integer counts per workgroup reduced in a
+ * fixed order: bit-identical run to run, no atomics.  Backward = one launch: d_depth, d_alpha (f32 [C,H,W], every element written
+ * once, zero where the pixel is unused or E <= 0) from d_out[1] = the gradient of loss on the device; it reads M from `out` as the
+ * forward left it (on the device), is exactly linear in d_out, and takes sign(0) = 0.  16-byte accesses where depth, alpha,
+ * depth_gt (and d_depth, d_alpha) are 16-byte and mask 4-byte aligned, scalar otherwise. */
+typedef struct {
+  const float* depth; const float* alpha; const float* depth_gt;
+  const unsigned char* mask;                 /* or NULL */
+  int C, H, W;
+  double scale;                              /* the reference's scene_scale */
+  double* out;                               /* [2]: loss, M (written by the forward, read by the backward) */
+  void* workspace; long workspace_bytes;     /* v3a_depth_loss_workspace_bytes(C, H, W), 8-byte aligned (forward only) */
+} v3a_depth_loss_args;
+long v3a_depth_loss_workspace_bytes(int C, int H, int W);   /* V3A_ERR_SHAPE for a non-positive or too large size */
+int v3a_depth_loss_forward(const v3a_depth_loss_args* a, void* stream);
+int v3a_depth_loss_backward(const v3a_depth_loss_args* a, const double* d_out, float* d_depth, float* d_alpha, void* stream);
 
 /* Splat activation (csrc/post_opt.hip), one thread per Gaussian: log-scales [U,3], raw quaternions [U,4] (xyzw, any length),
  * opacity logits [U] -> covariances [U,3,3] = R diag(exp(log_scale))^2 R^T with v3a_gaussian_adapter's quaternion order,

@@ -63,13 +63,24 @@ def build_text_encoder(args, device):
     return make_pipeline_text_encoder(UMT5TextEncoder(UMT5Config(), sd, device=device), AutoTokenizer.from_pretrained(tk))
 
 
-def refine(gaussians, clip_cl, pose, res, steps):
+def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0):
     from vist3a_amd import ops
     from vist3a_amd.post_opt import PostOptConfig, post_optimize
     with torch.no_grad():
         ff = ops.bilinear_cl(clip_cl, (res, res), align_corners=False)          # what Text23DGS.generate fed the reconstruction
         frames = ((ff[..., :3].float() + 1) / 2).clamp(0, 1).contiguous()       # [V,res,res,3] in [0,1]
-    g, _ = post_optimize(gaussians, frames, pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach(), PostOptConfig(), steps=steps)
+    cfg, extra = PostOptConfig(), {}
+    if depth_lambda > 0:
+        if not depth_dict or "depth" not in depth_dict or "conf_valid_mask" not in depth_dict:
+            raise ValueError("--post_opt_depth_lambda needs the reconstruction's depth_dict (depth, conf_valid_mask); this output has none")
+        # the depth head's map is z along the camera axis in the units of pose["extrinsic"]: what the
+        # rasteriser's depth channel accumulates, so it is the target as it stands
+        depths, masks = depth_dict["depth"][0, ..., 0].detach().float().contiguous(), depth_dict["conf_valid_mask"][0].detach().contiguous()
+        if tuple(depths.shape[-2:]) != tuple(frames.shape[1:3]) or tuple(masks.shape[-2:]) != tuple(frames.shape[1:3]):
+            raise ValueError(f"depth maps {tuple(depths.shape)} / masks {tuple(masks.shape)} do not match the frames {tuple(frames.shape)}")
+        cfg = PostOptConfig(depth_loss=True, depth_lambda=float(depth_lambda))
+        extra = dict(depths=depths, depth_masks=masks)
+    g, _ = post_optimize(gaussians, frames, pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach(), cfg, steps=steps, **extra)
     return g
 
 
@@ -113,7 +124,8 @@ def main(args):
         (save / "prompt.txt").write_text(prompt)
         g = out.gaussians
         if args.post_opt_steps > 0:   # against the frames the reconstruction saw, at the predicted context poses and intrinsics
-            g = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps)
+            g = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps, out.depth_dict,
+                       args.post_opt_depth_lambda)
         if not args.no_video:  # orbit video through the predicted context poses (reference :144-154)
             save_interpolated_video(out.pred_context_pose["extrinsic"], out.pred_context_pose["intrinsic"], 1, args.feedforward_resolution,
                                     args.feedforward_resolution, g, str(save), stitched.stitched_3d_model.decoder)

@@ -238,6 +238,17 @@ class PhotometricLossArgs(C.Structure):
     ]
 
 
+class DepthLossArgs(C.Structure):
+    _fields_ = [
+        ("depth", C.c_void_p), ("alpha", C.c_void_p), ("depth_gt", C.c_void_p),
+        ("mask", C.c_void_p),
+        ("C", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("scale", C.c_double),
+        ("out", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
 class AdamArgs(C.Structure):
     _fields_ = [
         ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
@@ -319,13 +330,16 @@ SYMBOLS = {
     "v3a_photometric_loss_planes_bytes": (C.c_long, [C.c_int] * 4),
     "v3a_photometric_loss_forward": (C.c_int, [C.POINTER(PhotometricLossArgs), C.c_void_p]),
     "v3a_photometric_loss_backward": (C.c_int, [C.POINTER(PhotometricLossArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v3a_depth_loss_workspace_bytes": (C.c_long, [C.c_int] * 3),
+    "v3a_depth_loss_forward": (C.c_int, [C.POINTER(DepthLossArgs), C.c_void_p]),
+    "v3a_depth_loss_backward": (C.c_int, [C.POINTER(DepthLossArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "v3a_splat_activate": (C.c_int, [C.c_void_p] * 3 + [C.c_long] + [C.c_void_p] * 3),
     "v3a_splat_activate_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),
     "v3a_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 26   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 27   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

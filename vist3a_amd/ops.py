@@ -1432,6 +1432,60 @@ def photometric_loss(pred: torch.Tensor, target: torch.Tensor, ssim_lambda: floa
     return _PhotometricLoss.apply(pred, target, float(ssim_lambda))
 
 
+class _DepthLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, alpha, depth_gt, mask, scale):
+        Cc, H, W = depth.shape
+        lib = L.load()
+        need = lib.v3a_depth_loss_workspace_bytes(Cc, H, W)
+        if need < 0:
+            L.check(int(need), f"v3a_depth_loss_workspace_bytes (shape {tuple(depth.shape)})")
+        dev = depth.device
+        ws = torch.empty((int(need) + 7) // 8, device=dev, dtype=torch.float64)
+        out = torch.empty(2, device=dev, dtype=torch.float64)
+        args = L.DepthLossArgs(_ptr(depth), _ptr(alpha), _ptr(depth_gt), _ptr(mask), Cc, H, W, float(scale), _ptr(out), _ptr(ws), ws.numel() * 8)
+        L.check(lib.v3a_depth_loss_forward(C.byref(args), _stream()), "v3a_depth_loss_forward")
+        ctx.save_for_backward(depth, alpha, depth_gt, mask, out)
+        ctx.scale = float(scale)
+        loss, count = out[0], out[1]
+        ctx.mark_non_differentiable(count)
+        return loss, count
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_loss, _d_count):
+        depth, alpha, depth_gt, mask, out = ctx.saved_tensors
+        Cc, H, W = depth.shape
+        d_out = d_loss.to(torch.float64).reshape(1).contiguous()
+        d_depth, d_alpha = torch.empty_like(depth), torch.empty_like(alpha)
+        args = L.DepthLossArgs(_ptr(depth), _ptr(alpha), _ptr(depth_gt), _ptr(mask), Cc, H, W, ctx.scale, _ptr(out), None, 0)
+        L.check(L.load().v3a_depth_loss_backward(C.byref(args), _ptr(d_out), _ptr(d_depth), _ptr(d_alpha), _stream()), "v3a_depth_loss_backward")
+        return d_depth, d_alpha, None, None, None
+
+
+def depth_loss(depth: torch.Tensor, alpha: torch.Tensor, depth_gt: torch.Tensor, mask: Optional[torch.Tensor] = None, scale: float = 1.0):
+    """The reference loop's depth term (simple_trainer.py:943-961) on dense maps (csrc/depth_loss.hip): `depth`, `alpha` f32 [C,H,W]
+    as gs_render returns them (depth = the alpha-weighted z), `depth_gt` f32 [C,H,W], `mask` bool / uint8 [C,H,W] (nonzero = use the
+    pixel) or None.  loss = scale * mean over the used pixels of |disp - 1 / depth_gt|, disp = 1 / E where E = depth /
+    max(alpha, 1e-10) > 0, else 0; a pixel is used where the mask is set and depth_gt is positive and finite.
+    -> (loss, count): float64 scalars on the device, count = the number of used pixels (0 gives loss 0 and zero gradients).
+    Differentiable with respect to `depth` and `alpha` (HIP backward, first order only); `depth_gt` and `mask` are constants."""
+    if depth_gt.requires_grad or (mask is not None and mask.requires_grad):
+        raise NotImplementedError("depth_loss: no gradient for depth_gt / mask (they are constants of the loss); detach them")
+    if depth.dim() != 3:
+        raise ValueError(f"depth_loss: depth must be [C,H,W], got {tuple(depth.shape)}")
+    _f32_dev(depth, "depth")
+    _f32_dev(alpha, "alpha", depth.shape)
+    _f32_dev(depth_gt, "depth_gt", depth.shape)
+    if mask is not None:
+        if not mask.is_cuda or mask.dtype not in (torch.bool, torch.uint8) or not mask.is_contiguous() or mask.shape != depth.shape:
+            raise ValueError(f"mask must be a contiguous bool or uint8 device tensor of shape {tuple(depth.shape)}, got {mask.dtype} "
+                             f"{tuple(mask.shape)} on {mask.device}")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)   # the same bytes (a bool is stored as 0 / 1), no copy
+    return _DepthLoss.apply(depth, alpha, depth_gt, mask, float(scale))
+
+
 class _SplatActivate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_scales, quats, logits):

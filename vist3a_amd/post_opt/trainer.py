@@ -4,9 +4,11 @@
 quaternions, opacity logits and harmonics, each with its Adam moments.  `post_optimize` is train() (:804-1152) with the features the
 reference switches off, or that need what this package does not have, left out (DESIGN.md section 7f lists them): one view per step,
 loss = 0.8 L1 + 0.2 (1 - SSIM) (:938-942), one Adam (eps 1e-15) per tensor, the means' rate decaying to 1 % over max_steps, no
-densification (:389-392).  Every step is ops.splat_activate -> ops.gs_render -> ops.photometric_loss -> backward -> ops.adam_step per
-trained tensor: HIP kernels throughout, torch only carries the autograd graph.  Nothing in the loop reads a value back to the host
-(apart from the rasteriser's own intersection count); the per-step loss, L1 and SSIM stay in a device tensor.
+densification (:389-392), optionally the depth term (:943-961, cfg.depth_loss: ops.depth_loss on the rasteriser's depth and alpha
+against a dense depth map per view).  Every step is ops.splat_activate -> ops.gs_render -> ops.photometric_loss (+ cfg.depth_lambda *
+ops.depth_loss with cfg.depth_loss) -> backward -> ops.adam_step per trained tensor: HIP kernels throughout, torch only carries the
+autograd graph.  Nothing in the loop reads a value back to the host (apart from the rasteriser's own intersection count); the
+per-step loss, L1, SSIM and, with cfg.depth_loss, the depth term stay in a device tensor.
 
 The harmonics stay ONE [U,3,K] tensor: the reference's sh0 / shN optimisers (rates lr_sh and lr_sh / 20) are one ops.adam_step with
 a period of K, which is the same arithmetic because Adam is elementwise."""
@@ -37,6 +39,9 @@ class PostOptConfig:
     betas: Tuple[float, float] = (0.9, 0.999)
     eps: float = 1e-15
     min_opacity: float = 0.01        # Gaussians at or below it are dropped at creation (:427)
+    depth_loss: bool = False         # :358-360; the term itself :943-961, here on dense maps (ops.depth_loss)
+    depth_lambda: float = 1e-2
+    scene_scale: float = 1.0         # multiplies the depth term (:426, :960)
     # ours
     params: Tuple[str, ...] = ("means", "scales", "quats", "opacities", "sh0", "shN")
     seed: int = 0
@@ -105,11 +110,17 @@ def splats_to_gaussians(splats: dict) -> Gaussians:
 
 
 def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.Tensor, intrinsics: torch.Tensor,
-                  cfg: Optional[PostOptConfig] = None, steps: Optional[int] = None, splats: Optional[dict] = None):
+                  cfg: Optional[PostOptConfig] = None, steps: Optional[int] = None, splats: Optional[dict] = None,
+                  depths: Optional[torch.Tensor] = None, depth_masks: Optional[torch.Tensor] = None):
     """Refine one scene's Gaussians against `images` (f32 [V,H,W,3] in [0,1], on the device) seen from `extrinsics` (camera-to-world
     [V,4,4]) with `intrinsics` (normalised [V,3,3]) - the decoder's conventions.  `steps` (default cfg.max_steps) steps of one view
     each; the means' learning-rate schedule always spans cfg.max_steps.  -> (Gaussians, log): the refined scene (rows at or below
-    cfg.min_opacity dropped) and a float64 device tensor [steps,3] of per-step (loss, l1, ssim)."""
+    cfg.min_opacity dropped) and a float64 device tensor of per-step (loss, l1, ssim), [steps,3], or with cfg.depth_loss
+    (loss, l1, ssim, depth_term), [steps,4]: loss is the total, depth_term the unweighted term.
+
+    With cfg.depth_loss the step's loss is photometric + cfg.depth_lambda * ops.depth_loss(rendered depth, alpha, depths[j],
+    depth_masks[j], cfg.scene_scale): `depths` f32 [V,H,W] on the device are z along the camera axis in the units of `extrinsics`,
+    `depth_masks` bool / uint8 [V,H,W] (or None: every pixel with a positive finite depth).  Without cfg.depth_loss `depths` is ignored."""
     cfg = cfg or PostOptConfig()
     _single(gaussians)
     for t, n in ((extrinsics, "extrinsics"), (intrinsics, "intrinsics")):
@@ -121,6 +132,17 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     if tuple(extrinsics.shape) != (V, 4, 4) or tuple(intrinsics.shape) != (V, 3, 3):
         raise ValueError(f"extrinsics [V,4,4] and intrinsics [V,3,3] must match the {V} images, got {tuple(extrinsics.shape)} and "
                          f"{tuple(intrinsics.shape)}")
+    if cfg.depth_loss:
+        if depths is None:
+            raise ValueError("post_optimize: cfg.depth_loss needs `depths` (f32 [V,H,W])")
+        if tuple(depths.shape) != (V, H, W) or depths.dtype != torch.float32:
+            raise ValueError(f"depths must be float32 [V,H,W] = {(V, H, W)} like the images, got {depths.dtype} {tuple(depths.shape)}")
+        if depth_masks is not None and (tuple(depth_masks.shape) != (V, H, W) or depth_masks.dtype not in (torch.bool, torch.uint8)):
+            raise ValueError(f"depth_masks must be bool or uint8 [V,H,W] = {(V, H, W)}, got {depth_masks.dtype} {tuple(depth_masks.shape)}")
+        if not depths.is_cuda or (depth_masks is not None and not depth_masks.is_cuda):
+            raise ValueError("depths and depth_masks must be on the device (the HIP path has no CPU fallback)")
+        depths = depths.detach().contiguous()
+        depth_masks = None if depth_masks is None else depth_masks.detach().contiguous()
     if not images.is_cuda:
         raise ValueError("images must be on the device (the HIP path has no CPU fallback)")
     steps = cfg.max_steps if steps is None else int(steps)
@@ -133,7 +155,7 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     view, campos, Kpix = _cameras(extrinsics, intrinsics, W, H, dev)
     images = images.contiguous()
     background = torch.zeros(3, device=dev, dtype=torch.float32)
-    log = torch.zeros(steps, 3, device=dev, dtype=torch.float64)
+    log = torch.zeros(steps, 4 if cfg.depth_loss else 3, device=dev, dtype=torch.float64)
     lrs = dict(means=cfg.lr_means, scales=cfg.lr_scales, quats=cfg.lr_quats, opacities=cfg.lr_opacities, sh=cfg.lr_sh)
     decay = 0.01 ** (1.0 / cfg.max_steps)
     ws = ops.GsWorkspace()
@@ -141,11 +163,17 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     try:
         for i, j in enumerate(view_order(V, steps, cfg.seed)):
             cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
-            color, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
+            color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
                                         sh_degree=sh_degree, sh_layout=1, background=background, clamp_rgb=True, workspace=ws)
             loss, l1, ssim = ops.photometric_loss(color, images[j:j + 1], cfg.ssim_lambda)
+            if cfg.depth_loss:
+                dterm, _ = ops.depth_loss(depth, alpha, depths[j:j + 1], None if depth_masks is None else depth_masks[j:j + 1], cfg.scene_scale)
+                loss = loss + cfg.depth_lambda * dterm
+                rec = [loss.detach(), l1.detach(), ssim.detach(), dterm.detach()]
+            else:
+                rec = [loss.detach(), l1.detach(), ssim.detach()]
             grads = torch.autograd.grad(loss, leaves)
-            log[i].copy_(torch.stack([loss.detach(), l1.detach(), ssim.detach()]))
+            log[i].copy_(torch.stack(rec))
             t = splats["step"] + 1
             with torch.no_grad():
                 for n, g in zip(trained, grads):

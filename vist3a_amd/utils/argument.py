@@ -43,6 +43,10 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
     g.add_argument("--post_opt_steps", type=int, default=0,
                    help="refine the predicted Gaussians for N steps against the frames the reconstruction was fed (AnySplat's post-optimisation, "
                         "vist3a_amd/post_opt) before gaussians.ply and the videos are written; 0 = off")
+    g.add_argument("--post_opt_depth_lambda", type=float, default=0.0,
+                   help="weight of the post-optimisation's depth term (the reference's depth_loss / depth_lambda, there 1e-2): an L1 in "
+                        "disparity between the rendered expected depth and the depth head's map of each view, on its confident pixels; "
+                        "0 = off")
     return p
 
 
