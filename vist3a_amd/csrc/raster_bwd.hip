@@ -13,8 +13,6 @@
 //                               2D covariance -> J, camera covariance -> world covariance; mean through J, the pixel mean,
 //                               the depth channel and the SH view direction; SH coefficients.
 // No atomics on floats anywhere: every sum has a fixed order, results are bit-identical run to run.
-#include <rocprim/device/device_scan.hpp>
-
 #include "common.h"
 #include "gs_raster.h"
 #include "../../include/vist3a_hip.h"
@@ -26,13 +24,6 @@ using namespace gs;
 constexpr int ROWF = 12;  // floats per row: d_means2d (2) d_conics (3) d_colors (4) d_opacity (1), padded to three 16-byte stores
 constexpr int BB = 128;   // Gaussians per backward round (4 waves x BB x 48 B of LDS partials)
 
-__host__ __device__ __forceinline__ float fast_exp(float x) {
-#ifdef __HIP_DEVICE_COMPILE__
-  return __expf(x);  // the forward's: both passes must see the same alpha
-#else
-  return expf(x);
-#endif
-}
 __host__ __device__ __forceinline__ float fast_rcp(float x) {
 #ifdef __HIP_DEVICE_COMPILE__
   return __builtin_amdgcn_rcpf(x);
@@ -70,27 +61,6 @@ __host__ __device__ __forceinline__ void blend_bwd_pair(float dx, float dy, floa
   }
 }
 
-// ---------------------------------------------------------------------------------------------- row slots
-struct CountP {
-  const int* radii; const float* means2d;
-  long CU;
-  int tw, th;
-  unsigned int* counts;
-};
-
-__global__ __launch_bounds__(256) void gs_bwd_count_kernel(CountP p) {
-  const long e = (long)blockIdx.x * 256 + threadIdx.x;
-  if (e >= p.CU) return;
-  unsigned int n = 0;
-  const int r = p.radii[e];
-  if (r > 0) {
-    int x0, x1, y0, y1;
-    tile_bounds(p.means2d[2 * e], p.means2d[2 * e + 1], r, p.tw, p.th, x0, x1, y0, y1);
-    n = (unsigned int)((x1 - x0) * (y1 - y0));
-  }
-  p.counts[e] = n;
-}
-
 // ---------------------------------------------------------------------------------------------- blend backward
 struct BlendBwdP {
   const int* radii; const float* means2d; const float* conics; const float* colors; const float* opac;
@@ -124,20 +94,8 @@ __device__ __forceinline__ unsigned int row_slot(const BlendBwdP& p, unsigned in
   return slot < p.n_isect ? slot : ~0u;
 }
 
-// stage one Gaussian of a tile list into LDS (the forward's three 16-byte records); an id outside the call reads as transparent
-__device__ __forceinline__ void stage_gaussian(const BlendBwdP& p, unsigned int id, int cam, f32x4* dst) {
-  f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = a, col = a;
-  const unsigned int gi = id - (unsigned int)cam * (unsigned int)p.U;
-  if (id < p.CU && gi < (unsigned int)p.U) {
-    a = f32x4{p.means2d[2L * id], p.means2d[2L * id + 1], p.opac[gi], 0.f};
-    c = f32x4{p.conics[3L * id], p.conics[3L * id + 1], p.conics[3L * id + 2], 0.f};
-    col = *(const f32x4*)(p.colors + 4L * id);
-  }
-  dst[0] = a; dst[1] = c; dst[2] = col;
-}
-
 __global__ __launch_bounds__(256) void gs_blend_bwd_kernel(BlendBwdP p) {
-  __shared__ f32x4 s_g[256 * 3];        // {x, y, opacity, -} {conic a, b, c, -} {r, g, b, depth}
+  __shared__ f32x4 s_g[256 * 3];        // stage_gaussian's records
   __shared__ f32x4 s_part[4][BB][3];    // per wave, per Gaussian of the round: the ten reduced terms
   __shared__ unsigned int s_slot[BB];
   __shared__ unsigned int s_stop;
@@ -150,31 +108,11 @@ __global__ __launch_bounds__(256) void gs_blend_bwd_kernel(BlendBwdP p) {
   const unsigned int e = min(p.offs[blockIdx.x + 1], p.n_isect), s = min(p.offs[blockIdx.x], e);
   if (tid == 0) s_stop = s;
 
-  // ---- front to back, the forward's loop: final T, pre-clamp colour, and the list index this pixel stopped at
-  float T = 1.f, r = 0.f, g = 0.f, b = 0.f;
-  unsigned int stop = inside ? e : s;
-  bool done = !inside;
-  for (unsigned int base = s; base < e; base += 256) {
-    if (__syncthreads_and(done)) break;  // also the barrier that protects s_g from the previous round's readers
-    const unsigned int n = min(256u, e - base);
-    if ((unsigned int)tid < n) stage_gaussian(p, p.ids[base + tid], cam, s_g + 3 * tid);
-    __syncthreads();
-    if (!done) {
-      for (unsigned int k = 0; k < n; ++k) {
-        const f32x4 a = s_g[3 * k], c = s_g[3 * k + 1];
-        const float dx = a[0] - px, dy = a[1] - py;
-        const float sigma = 0.5f * (c[0] * dx * dx + c[2] * dy * dy) + c[1] * dx * dy;
-        const float alpha = fminf(0.999f, a[2] * fast_exp(-sigma));
-        if (sigma < 0.f || alpha < 1.f / 255.f) continue;
-        const float nT = T * (1.f - alpha);
-        if (nT <= 1e-4f) { done = true; stop = base + k; break; }
-        const float vis = alpha * T;
-        const f32x4 col = s_g[3 * k + 2];
-        r += col[0] * vis; g += col[1] * vis; b += col[2] * vis;
-        T = nT;
-      }
-    }
-  }
+  // ---- front to back, the forward's walk: final T, pre-clamp colour, and the list index this pixel stopped at
+  float T, acc[3];
+  unsigned int stop;
+  composite_walk<3>(p, s_g, cam, s, e, px, py, inside, T, acc, stop);
+  float r = acc[0], g = acc[1], b = acc[2];
   // incoming gradients of this pixel; the clamp passes them where the un-clamped value lies in [0, 1], as torch.clamp does
   float gr[4] = {0.f, 0.f, 0.f, 0.f}, gT = 0.f;
   const float Tfin = T;
@@ -211,17 +149,14 @@ __global__ __launch_bounds__(256) void gs_blend_bwd_kernel(BlendBwdP p) {
     __syncthreads();
     for (int k = n - 1; k >= 0; --k) {
       const f32x4 a = s_g[3 * k], c = s_g[3 * k + 1];
-      const float dx = a[0] - px, dy = a[1] - py;
-      const float sigma = 0.5f * (c[0] * dx * dx + c[2] * dy * dy) + c[1] * dx * dy;
-      const float ex = fast_exp(-sigma);
-      const float alpha = fminf(0.999f, a[2] * ex);
-      const bool valid = (base + (unsigned int)k < stop) && !(sigma < 0.f || alpha < 1.f / 255.f);
+      float ex, alpha;
+      const bool valid = pair_alpha(a, c, px, py, ex, alpha) && (base + (unsigned int)k < stop);
       f32x4 o0 = {0.f, 0.f, 0.f, 0.f}, o1 = o0, o2 = o0;
       if (__any(valid)) {  // wave-uniform: a wave is four pixel rows, most Gaussians touch few of them
         float v[10];
 #pragma unroll
         for (int i = 0; i < 10; ++i) v[i] = 0.f;
-        if (valid) blend_bwd_pair(dx, dy, c[0], c[1], c[2], a[2], ex, alpha, s_g[3 * k + 2], gr, gT, Tfin, T, S, v);
+        if (valid) blend_bwd_pair(a[0] - px, a[1] - py, c[0], c[1], c[2], a[2], ex, alpha, s_g[3 * k + 2], gr, gT, Tfin, T, S, v);
 #pragma unroll
         for (int i = 0; i < 10; ++i) v[i] = wave_sum_lane63(v[i]);
         o0 = f32x4{v[0], v[1], v[2], v[3]}; o1 = f32x4{v[4], v[5], v[6], v[7]}; o2 = f32x4{v[8], v[9], 0.f, 0.f};
@@ -282,18 +217,10 @@ BLayout blayout(long CU, long cap) {
   auto take = [&](size_t b) { size_t o = off; off += al256(b); return o; };
   l.counts = take(4 * (size_t)CU); l.incl = take(4 * (size_t)CU);
   l.rows = take(sizeof(float) * ROWF * (size_t)cap);
-  size_t t = 0;
-  (void)rocprim::inclusive_scan(nullptr, t, (unsigned int*)nullptr, (unsigned int*)nullptr, (size_t)CU, rocprim::plus<unsigned int>());
-  l.tmp_bytes = t;
-  l.tmp = take(t);
+  l.tmp_bytes = scan_tmp_bytes(CU);
+  l.tmp = take(l.tmp_bytes);
   l.total = off;
   return l;
-}
-
-bool dims_ok(long U, int C, int width, int height, long max_isect) {  // the forward's limits
-  if (U <= 0 || C <= 0 || width <= 0 || height <= 0 || max_isect <= 0 || max_isect >= (1L << 31)) return false;
-  const long nt = (long)((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
-  return U * (long)C < (1L << 32) && nt * C < (1L << 24);
 }
 
 // ---------------------------------------------------------------------------------------------- projection backward
@@ -367,33 +294,17 @@ __host__ __device__ __forceinline__ void proj_bwd_entry(const ProjGeo& q, const 
   const float* V = q.V;
   const float R00 = V[0], R01 = V[1], R02 = V[2], R10 = V[4], R11 = V[5], R12 = V[6], R20 = V[8], R21 = V[9], R22 = V[10];
   const float mx = m[0], my = m[1], mz = m[2];
-  const float x = R00 * mx + R01 * my + R02 * mz + V[3];
-  const float y = R10 * mx + R11 * my + R12 * mz + V[7];
-  const float z = R20 * mx + R21 * my + R22 * mz + V[11];
-  const float s00 = sw[0], s01 = sw[1], s02 = sw[2], s11 = sw[3], s12 = sw[4], s22 = sw[5];
   // the forward's chain up to the 2D covariance
-  const float a00 = R00 * s00 + R01 * s01 + R02 * s02, a01 = R00 * s01 + R01 * s11 + R02 * s12, a02 = R00 * s02 + R01 * s12 + R02 * s22;
-  const float a10 = R10 * s00 + R11 * s01 + R12 * s02, a11 = R10 * s01 + R11 * s11 + R12 * s12, a12 = R10 * s02 + R11 * s12 + R12 * s22;
-  const float a20 = R20 * s00 + R21 * s01 + R22 * s02, a21 = R20 * s01 + R21 * s11 + R22 * s12, a22 = R20 * s02 + R21 * s12 + R22 * s22;
-  const float c00 = a00 * R00 + a01 * R01 + a02 * R02, c01 = a00 * R10 + a01 * R11 + a02 * R12, c02 = a00 * R20 + a01 * R21 + a02 * R22;
-  const float c11 = a10 * R10 + a11 * R11 + a12 * R12, c12 = a10 * R20 + a11 * R21 + a12 * R22;
-  const float c22 = a20 * R20 + a21 * R21 + a22 * R22;
-  const float fx = q.Kc[0], fy = q.Kc[4], cx = q.Kc[2], cy = q.Kc[5];
-  const float tfx = 0.5f * q.W / fx, tfy = 0.5f * q.H / fy;
-  const float lxp = (q.W - cx) / fx + 0.3f * tfx, lxn = cx / fx + 0.3f * tfx;
-  const float lyp = (q.H - cy) / fy + 0.3f * tfy, lyn = cy / fy + 0.3f * tfy;
-  const float rz = 1.f / z, rz2 = rz * rz;
+  float x, y, z;
+  to_camera(V, mx, my, mz, x, y, z);
+  const ProjEntry e = project_entry(V, q.Kc, q.W, q.H, q.eps2d, x, y, z, sw[0], sw[1], sw[2], sw[3], sw[4], sw[5]);
+  const float rz = e.rz, rz2 = e.rz2, fx = e.fx, fy = e.fy, tx = e.tx, ty = e.ty;
+  const float lxp = e.lxp, lxn = e.lxn, lyp = e.lyp, lyn = e.lyn, j00 = e.j00, j02 = e.j02, j11 = e.j11, j12 = e.j12;
+  const float t00 = e.t00, t01 = e.t01, t02 = e.t02, t10 = e.t10, t11 = e.t11, t12 = e.t12;
   const float xz = x * rz, yz = y * rz;
-  const float cxz = fminf(lxp, fmaxf(-lxn, xz)), cyz = fminf(lyp, fmaxf(-lyn, yz));
-  const float tx = z * cxz, ty = z * cyz;
-  const float j00 = fx * rz, j02 = -fx * tx * rz2, j11 = fy * rz, j12 = -fy * ty * rz2;
-  const float t00 = j00 * c00 + j02 * c02, t01 = j00 * c01 + j02 * c12, t02 = j00 * c02 + j02 * c22;   // J Cc, row 0
-  const float t10 = j11 * c01 + j12 * c02, t11 = j11 * c11 + j12 * c12, t12 = j11 * c12 + j12 * c22;   // row 1
-  const float q00 = t00 * j00 + t02 * j02 + q.eps2d;
-  const float q01 = t01 * j11 + t02 * j12;
-  const float q11 = t11 * j11 + t12 * j12 + q.eps2d;
-  const float id = 1.f / (q00 * q11 - q01 * q01);
-  const float X00 = q11 * id, X01 = -q01 * id, X11 = q00 * id;  // the conic
+  const float cxz = fminf(lxp, fmaxf(-lxn, xz)), cyz = fminf(lyp, fmaxf(-lyn, yz));  // tx = z * cxz, ty = z * cyz
+  const float id = 1.f / e.det;
+  const float X00 = e.q11 * id, X01 = -e.q01 * id, X11 = e.q00 * id;  // the conic
   // conic = Q^-1:  dL/dQ = -X G X with G = [[va, vb/2], [vb/2, vc]]  (symmetric 2x2; M01 stands for both off-diagonal positions)
   const float G00 = vcon[0], G01 = 0.5f * vcon[1], G11 = vcon[2];
   const float h00 = X00 * G00 + X01 * G01, h01 = X00 * G01 + X01 * G11, h10 = X01 * G00 + X11 * G01, h11 = X01 * G01 + X11 * G11;
@@ -426,14 +337,8 @@ __host__ __device__ __forceinline__ void proj_bwd_entry(const ProjGeo& q, const 
   const float ux = dx * inv, uy = dy * inv, uz = dz * inv;
   float bas[NB];
   sh_eval<DEG>(ux, uy, uz, bas);
-  float r = 0.f, gg = 0.f, b = 0.f;
-  if (sh_layout == 0) {
-#pragma unroll
-    for (int k = 0; k < NB; ++k) { r += bas[k] * s[3 * k]; gg += bas[k] * s[3 * k + 1]; b += bas[k] * s[3 * k + 2]; }
-  } else {
-#pragma unroll
-    for (int k = 0; k < NB; ++k) { r += bas[k] * s[k]; gg += bas[k] * s[sh_k + k]; b += bas[k] * s[2 * sh_k + k]; }
-  }
+  float r, gg, b;
+  sh_color<DEG>(bas, s, sh_layout, sh_k, r, gg, b);
   const float vr = (r + 0.5f >= 0.f) ? vcol[0] : 0.f, vg = (gg + 0.5f >= 0.f) ? vcol[1] : 0.f, vb = (b + 0.5f >= 0.f) ? vcol[2] : 0.f;
   float gk[NB];
 #pragma unroll
@@ -469,10 +374,7 @@ __global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
   const int row = 3 * p.sh_k;
   const int nrow = min(64, p.U - g0);
   const int total = nrow * row;
-  {
-    const float* src = p.sh + (long)g0 * row;
-    for (int i = lane; i < total; i += 64) s_sh[i] = src[i];
-  }
+  stage_sh_rows(s_sh, p.sh + (long)g0 * row, total, lane);
   __syncthreads();
   float* s = s_sh + lane * row;
   if (g < p.U) {
@@ -515,12 +417,6 @@ __global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
   for (int i = lane; i < total; i += 64) dst[i] = s_sh[i];
 }
 
-template <int DEG>
-void launch_project_bwd(const ProjBwdP& p, hipStream_t stream) {
-  const size_t lds = (size_t)64 * 3 * p.sh_k * sizeof(float);
-  hipLaunchKernelGGL(gs_project_bwd_kernel<DEG>, dim3((unsigned)((p.U + 63) / 64)), dim3(64), lds, stream, p);
-}
-
 }  // namespace
 
 extern "C" long v3a_gs_rasterize_backward_workspace_bytes(long U, int C, int width, int height, long max_isect) {
@@ -535,9 +431,8 @@ extern "C" int v3a_gs_rasterize_backward(const v3a_gs_rasterize_backward_args* a
   if (a->n_isect < 0 || (a->n_isect > 0 && !a->flatten_ids)) return V3A_ERR_ARG;
   if (!dims_ok(a->U, a->C, a->width, a->height, a->n_isect > 0 ? a->n_isect : 1)) return V3A_ERR_SHAPE;
   hipStream_t stream = (hipStream_t)stream_;
-  const int tw = (a->width + TILE - 1) / TILE, th = (a->height + TILE - 1) / TILE, ntiles = tw * th;
+  const TileGrid tg = tile_grid(a->width, a->height);
   const long CU = a->U * a->C;
-  const int nt_all = ntiles * a->C;
   const BLayout l = blayout(CU, a->n_isect > 0 ? a->n_isect : 1);
   if ((size_t)a->workspace_bytes < l.total) return V3A_ERR_WORKSPACE;
   char* ws = (char*)a->workspace;
@@ -545,15 +440,11 @@ extern "C" int v3a_gs_rasterize_backward(const v3a_gs_rasterize_backward_args* a
   unsigned int* incl = (unsigned int*)(ws + l.incl);
   float* rows = (float*)(ws + l.rows);
   const unsigned gb = (unsigned)((CU + 255) / 256);
-  CountP cp = {a->radii, a->means2d, CU, tw, th, counts};
-  hipLaunchKernelGGL(gs_bwd_count_kernel, dim3(gb), dim3(256), 0, stream, cp);
-  size_t tb = l.tmp_bytes;
-  if (rocprim::inclusive_scan(ws + l.tmp, tb, counts, incl, (size_t)CU, rocprim::plus<unsigned int>(), stream) != hipSuccess)
-    return V3A_ERR_LAUNCH;
+  if (!count_and_scan({a->radii, a->means2d, CU, tg.tw, tg.th, counts}, incl, ws + l.tmp, l.tmp_bytes, stream)) return V3A_ERR_LAUNCH;
   BlendBwdP bp = {a->radii, a->means2d, a->conics, a->colors, a->opacities, a->tile_offsets, a->flatten_ids, counts, incl, a->background,
                   a->d_color, a->d_depth, a->d_alpha, rows, (unsigned int)a->n_isect, (unsigned int)CU, (int)a->U, a->width, a->height,
-                  tw, th, ntiles, a->clamp_rgb};
-  if (a->n_isect > 0) hipLaunchKernelGGL(gs_blend_bwd_kernel, dim3((unsigned)nt_all), dim3(256), 0, stream, bp);
+                  tg.tw, tg.th, tg.ntiles, a->clamp_rgb};
+  if (a->n_isect > 0) hipLaunchKernelGGL(gs_blend_bwd_kernel, dim3((unsigned)(tg.ntiles * a->C)), dim3(256), 0, stream, bp);
   RowSumP rp = {counts, incl, rows, CU, (unsigned int)a->n_isect, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial};
   hipLaunchKernelGGL(gs_rowsum_kernel, dim3(gb), dim3(256), 0, stream, rp);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
@@ -563,20 +454,11 @@ extern "C" int v3a_gs_project_backward(const v3a_gs_project_backward_args* a, vo
   if (!a || !a->means || !a->covars || !a->sh || !a->viewmat || !a->campos || !a->K || !a->radii || !a->d_means2d || !a->d_conics ||
       !a->d_colors || !a->d_opacity_partial || !a->d_means || !a->d_covars || !a->d_sh || !a->d_opacities)
     return V3A_ERR_ARG;
-  if (a->U < 0 || a->C <= 0 || a->width <= 0 || a->height <= 0 || a->U >= (1L << 31)) return V3A_ERR_SHAPE;
-  if (a->sh_degree < 0 || a->sh_degree > 4 || a->sh_k < (a->sh_degree + 1) * (a->sh_degree + 1) || a->sh_k > 64) return V3A_ERR_SHAPE;
-  if (a->sh_layout != 0 && a->sh_layout != 1) return V3A_ERR_ARG;
+  if (const int rc = check_sh_args(*a)) return rc;
   if (a->U == 0) return V3A_OK;
   ProjBwdP p = {a->means, a->covars, a->sh, a->viewmat, a->campos, a->K, a->sh_layout, a->sh_k, (int)a->U, a->C, a->width, a->height,
                 a->eps2d, a->radii, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial, a->d_means, a->d_covars, a->d_sh,
                 a->d_opacities};
-  hipStream_t st = (hipStream_t)stream;
-  switch (a->sh_degree) {
-    case 0: launch_project_bwd<0>(p, st); break;
-    case 1: launch_project_bwd<1>(p, st); break;
-    case 2: launch_project_bwd<2>(p, st); break;
-    case 3: launch_project_bwd<3>(p, st); break;
-    default: launch_project_bwd<4>(p, st); break;
-  }
+  dispatch_sh_degree(a->sh_degree, [&](auto d) { launch_sh_waves(gs_project_bwd_kernel<decltype(d)::value>, p, (hipStream_t)stream); });
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

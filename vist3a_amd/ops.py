@@ -962,21 +962,25 @@ def unipc_cfg_step(dit_out: torch.Tensor, tok: Optional[torch.Tensor], sample: t
 
 
 # ------------------------------------------------------------------------------------------------ 3DGS rasteriser
+def _gs_scene_args(means, covars, sh, viewmat, campos, K, sh_layout):
+    """What gs_project and gs_project_backward check of their tensors -> (cameras, Gaussians, sh_k)."""
+    for t, n in ((means, "means"), (covars, "covars"), (sh, "sh"), (viewmat, "viewmat"), (campos, "campos"), (K, "K")):
+        if t.dtype != f32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"{n}: contiguous fp32 device tensor required")
+    Cn = 1 if viewmat.dim() == 2 else viewmat.shape[0]
+    if campos.numel() != 3 * Cn or K.numel() != 9 * Cn or viewmat.numel() != 16 * Cn:
+        raise ValueError("viewmat / campos / K disagree on the number of cameras")
+    return Cn, means.shape[0], sh.shape[2] if sh_layout == 1 else sh.shape[1]
+
+
 def gs_project(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, viewmat: torch.Tensor, campos: torch.Tensor,
                K: torch.Tensor, width: int, height: int, *, sh_degree: int = 4, sh_layout: int = 1, near_plane: float = 1e-10,
                far_plane: float = 1e10, radius_clip: float = 0.1, eps2d: float = 0.3):
     """fully_fused_projection + SH colours for C cameras at once (viewmat [C,4,4], campos [C,3], K [C,3,3] -> outputs [C,U,...])
     or one camera (viewmat [4,4] -> outputs [U,...]).  sh: [U,3,K] (sh_layout=1, Gaussians.harmonics) or [U,K,3] (0)."""
-    for t, n in ((means, "means"), (covars, "covars"), (sh, "sh"), (viewmat, "viewmat"), (campos, "campos"), (K, "K")):
-        if t.dtype != f32 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"{n}: contiguous fp32 device tensor required")
-    single = viewmat.dim() == 2
-    Cn = 1 if single else viewmat.shape[0]
-    if campos.numel() != 3 * Cn or K.numel() != 9 * Cn or viewmat.numel() != 16 * Cn:
-        raise ValueError("viewmat / campos / K disagree on the number of cameras")
-    U, dev = means.shape[0], means.device
-    sh_k = sh.shape[2] if sh_layout == 1 else sh.shape[1]
-    lead = () if single else (Cn,)
+    Cn, U, sh_k = _gs_scene_args(means, covars, sh, viewmat, campos, K, sh_layout)
+    dev = means.device
+    lead = () if viewmat.dim() == 2 else (Cn,)
     radii = torch.empty(*lead, U, device=dev, dtype=torch.int32)
     e = lambda *s: torch.empty(*lead, *s, device=dev, dtype=f32)
     m2, dep, con, col = e(U, 2), e(U), e(U, 3), e(U, 4)
@@ -986,23 +990,32 @@ def gs_project(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, view
     return dict(radii=radii, means2d=m2, depths=dep, conics=con, colors=col)
 
 
-class GsWorkspace:
-    """Grow-only scratch for v3a_gs_rasterize, shared by the camera batches of one video."""
+class _GsScratch:
+    """Grow-only device scratch sized by one of the library's workspace queries, shared by the camera batches of one video."""
+    query, min_cap = "", 0
 
     def __init__(self):
         self.buf, self.cap, self.key = None, 0, None
-        self.bwd = None  # GsBwdWorkspace, created by the first gs_render backward that is handed this workspace
 
     def get(self, U, Cn, width, height, need):
         key = (U, Cn, width, height)
         if self.buf is None or self.key != key or need > self.cap:
-            self.cap = max(int(need * 1.25), 1 << 20)
-            nbytes = L.load().v3a_gs_rasterize_workspace_bytes(U, Cn, width, height, self.cap)
+            self.cap = max(int(need * 1.25), self.min_cap)
+            nbytes = getattr(L.load(), self.query)(U, Cn, width, height, self.cap)
             if nbytes < 0:
-                L.check(int(nbytes), "v3a_gs_rasterize_workspace_bytes")
+                L.check(int(nbytes), self.query)
             self.buf, self.key = None, key
             self.buf = torch.empty(nbytes, device="cuda", dtype=torch.uint8)
         return self.buf
+
+
+class GsWorkspace(_GsScratch):
+    """Scratch for v3a_gs_rasterize."""
+    query, min_cap = "v3a_gs_rasterize_workspace_bytes", 1 << 20
+
+    def __init__(self):
+        super().__init__()
+        self.bwd = None  # GsBwdWorkspace, created by the first gs_render backward that is handed this workspace
 
 
 def gs_rasterize(proj: dict, opacities: torch.Tensor, width: int, height: int, *, background: Optional[torch.Tensor] = None,
@@ -1046,23 +1059,10 @@ def gs_rasterize(proj: dict, opacities: torch.Tensor, width: int, height: int, *
     return out
 
 
-class GsBwdWorkspace:
-    """Grow-only scratch for v3a_gs_rasterize_backward: two counters per camera-Gaussian entry and one 48-byte row per
-    intersection (the price of summing without atomics: every (Gaussian, tile) contribution is stored once, then added in order)."""
-
-    def __init__(self):
-        self.buf, self.cap, self.key = None, 0, None
-
-    def get(self, U, Cn, width, height, need):
-        key = (U, Cn, width, height)
-        if self.buf is None or self.key != key or need > self.cap:
-            self.cap = max(int(need * 1.25), 1 << 16)
-            nbytes = L.load().v3a_gs_rasterize_backward_workspace_bytes(U, Cn, width, height, self.cap)
-            if nbytes < 0:
-                L.check(int(nbytes), "v3a_gs_rasterize_backward_workspace_bytes")
-            self.buf, self.key = None, key
-            self.buf = torch.empty(nbytes, device="cuda", dtype=torch.uint8)
-        return self.buf
+class GsBwdWorkspace(_GsScratch):
+    """Scratch for v3a_gs_rasterize_backward: two counters per camera-Gaussian entry and one 48-byte row per intersection (the
+    price of summing without atomics: every (Gaussian, tile) contribution is stored once, then added in order)."""
+    query, min_cap = "v3a_gs_rasterize_backward_workspace_bytes", 1 << 16
 
 
 def _gs_f32(t: torch.Tensor, name: str, numel: int) -> None:
@@ -1117,14 +1117,7 @@ def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Ten
     """Backward of gs_project: the entry gradients of gs_rasterize_backward (or any dict with d_means2d, d_conics, d_colors,
     d_opacity) -> (d_means [U,3], d_covars [U,3,3], d_sh like sh, d_opacities [U]), summed over the cameras in index order.
     Cameras are constants: there is no gradient for viewmat / campos / K."""
-    for t, n in ((means, "means"), (covars, "covars"), (sh, "sh"), (viewmat, "viewmat"), (campos, "campos"), (K, "K")):
-        if t.dtype != f32 or not t.is_cuda or not t.is_contiguous():
-            raise ValueError(f"{n}: contiguous fp32 device tensor required")
-    Cn = 1 if viewmat.dim() == 2 else viewmat.shape[0]
-    if campos.numel() != 3 * Cn or K.numel() != 9 * Cn or viewmat.numel() != 16 * Cn:
-        raise ValueError("viewmat / campos / K disagree on the number of cameras")
-    U = means.shape[0]
-    sh_k = sh.shape[2] if sh_layout == 1 else sh.shape[1]
+    Cn, U, sh_k = _gs_scene_args(means, covars, sh, viewmat, campos, K, sh_layout)
     if covars.numel() != 9 * U or sh.numel() != 3 * sh_k * U:
         raise ValueError("means / covars / sh disagree on the number of Gaussians")
     if radii.dtype != torch.int32 or not radii.is_contiguous() or radii.numel() != Cn * U:
