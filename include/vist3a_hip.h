@@ -658,6 +658,37 @@ long v3a_depth_loss_workspace_bytes(int C, int H, int W);   /* V3A_ERR_SHAPE for
 int v3a_depth_loss_forward(const v3a_depth_loss_args* a, void* stream);
 int v3a_depth_loss_backward(const v3a_depth_loss_args* a, const double* d_out, float* d_depth, float* d_alpha, void* stream);
 
+/* Bilateral-grid colour compensation (csrc/bilagrid.hip; lib_bilagrid.py::BilateralGrid / slice / total_variation_loss, one grid per
+ * image): rgb f32 [N,H,W,3], grids f32 [N,L,GY,GX,12] coefficient-minor (coefficient 4c + k = row c, column k of the 3x4 matrix),
+ * GX, GY, L >= 2 (smaller: V3A_ERR_SHAPE; the reference degenerates silently), N H W 3 and N L GY GX 12 < 2^31.  Per pixel (i, j) in
+ * fp64: x = (j + 0.5) / W, y = (i + 0.5) / H, gray = 0.299f r + 0.587f g + 0.114f b; the grid is sampled as
+ * grid_sample(bilinear, align_corners=True, border) at (x (GX-1), y (GY-1), clamp(gray (L-1), 0, L-1)) and
+ * out[c] = A[c][0] r + A[c][1] g + A[c][2] b + A[c][3], rounded to f32 once.  Backward: d_rgb (through the matrix and through the
+ * guidance coordinate, whose term is exactly 0 where gray (L-1) <= 0 or >= L-1) and d_grids (a gather, one workgroup per vertex,
+ * fixed-order reduction, no atomics: every element written exactly once, zeros included); either may be NULL.  Both are
+ * bit-identical run to run and exactly linear in d_out. */
+typedef struct {
+  const float* rgb; const float* grids;
+  int N, H, W;
+  int GX, GY, L;
+} v3a_bilagrid_slice_args;
+int v3a_bilagrid_slice_forward(const v3a_bilagrid_slice_args* a, float* out, void* stream);
+int v3a_bilagrid_slice_backward(const v3a_bilagrid_slice_args* a, const float* d_out, float* d_rgb, float* d_grids, void* stream);
+
+/* Total variation of grids f32 [V,L,GY,GX,12] (total_variation_loss): for each of the axes L, GY, GX the sum of squared forward
+ * differences over 12 * (L GY GX with that axis' size - 1), added and divided by V -> out[0] (fp64).  Forward = two launches, fp64
+ * partials per workgroup reduced in a fixed order.  Backward = one launch, d_grids (f32, every element written once) from
+ * d_out[1] on the device, exactly linear in it. */
+typedef struct {
+  const float* grids;
+  int V, GX, GY, L;
+  double* out;                               /* [1] (forward only) */
+  void* workspace; long workspace_bytes;     /* v3a_bilagrid_tv_workspace_bytes(V, GX, GY, L), 8-byte aligned (forward only) */
+} v3a_bilagrid_tv_args;
+long v3a_bilagrid_tv_workspace_bytes(int V, int GX, int GY, int L);   /* V3A_ERR_SHAPE for a size under 2 or too large */
+int v3a_bilagrid_tv_forward(const v3a_bilagrid_tv_args* a, void* stream);
+int v3a_bilagrid_tv_backward(const v3a_bilagrid_tv_args* a, const double* d_out, float* d_grids, void* stream);
+
 /* Splat activation (csrc/post_opt.hip), one thread per Gaussian: log-scales [U,3], raw quaternions [U,4] (xyzw, any length),
  * opacity logits [U] -> covariances [U,3,3] = R diag(exp(log_scale))^2 R^T with v3a_gaussian_adapter's quaternion order,
  * normalisation and product, opacities [U] = sigmoid.  Backward: closed form from (d_covars, d_opacities); d_covars is contracted

@@ -63,7 +63,7 @@ def build_text_encoder(args, device):
     return make_pipeline_text_encoder(UMT5TextEncoder(UMT5Config(), sd, device=device), AutoTokenizer.from_pretrained(tk))
 
 
-def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0):
+def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False):
     from vist3a_amd import ops
     from vist3a_amd.post_opt import PostOptConfig, post_optimize
     with torch.no_grad():
@@ -80,6 +80,7 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
             raise ValueError(f"depth maps {tuple(depths.shape)} / masks {tuple(masks.shape)} do not match the frames {tuple(frames.shape)}")
         cfg = PostOptConfig(depth_loss=True, depth_lambda=float(depth_lambda))
         extra = dict(depths=depths, depth_masks=masks)
+    cfg.use_bilateral_grid = bool(bilateral_grid)
     g, _ = post_optimize(gaussians, frames, pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach(), cfg, steps=steps, **extra)
     return g
 
@@ -125,7 +126,7 @@ def main(args):
         g = out.gaussians
         if args.post_opt_steps > 0:   # against the frames the reconstruction saw, at the predicted context poses and intrinsics
             g = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps, out.depth_dict,
-                       args.post_opt_depth_lambda)
+                       args.post_opt_depth_lambda, args.post_opt_bilateral_grid)
         if not args.no_video:  # orbit video through the predicted context poses (reference :144-154)
             save_interpolated_video(out.pred_context_pose["extrinsic"], out.pred_context_pose["intrinsic"], 1, args.feedforward_resolution,
                                     args.feedforward_resolution, g, str(save), stitched.stitched_3d_model.decoder)

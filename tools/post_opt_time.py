@@ -1,7 +1,10 @@
 """One post-optimisation step (vist3a_amd/post_opt) at the sizes of tools/raster_bwd_time.py (448^2, 1M Gaussians, SH degree 4), one camera
 per step as the loop runs it.  Prints one JSON line: milliseconds (median of --iters after --warmup) of the five parts of a step -
 activation, render forward, loss, backward (loss + render + activation), Adam over the five tensors - and the Adam launch on the
-harmonics against a `copy_` of the same bytes (28 B per element: p, m, v read and written, g read; the yardstick of tools/norm_time.py)."""
+harmonics against a `copy_` of the same bytes (28 B per element: p, m, v read and written, g read; the yardstick of tools/norm_time.py).
+With --bilateral_grid the step runs as with cfg.use_bilateral_grid (21 views' grids of the default shape): the slice and the
+total-variation launches are timed as a part of their own ("bilagrid": both forwards; their backwards fall into "backward", the
+grid's Adam into "adam")."""
 import argparse
 import json
 import math
@@ -19,6 +22,7 @@ def main():
     ap.add_argument("--size", type=int, default=448)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--bilateral_grid", action="store_true")
     a = ap.parse_args()
     from vist3a_amd import ops
     U, W, H = a.gaussians, a.size, a.size
@@ -35,23 +39,33 @@ def main():
     campos = torch.linalg.inv(view)[:3, 3].contiguous().cuda()[None]
     view, K = view.cuda()[None], torch.tensor([[400.0, 0, W / 2], [0, 440.0, H / 2], [0, 0, 1.0]]).cuda()[None]
     target, bg, ws = torch.rand(1, H, W, 3, device="cuda"), torch.zeros(3, device="cuda"), ops.GsWorkspace()
-    names = ("activation", "render_forward", "loss", "backward", "adam")
+    names = ("activation", "render_forward", "bilagrid", "loss", "backward", "adam")
+    grids = ops.bilagrid_identity(21, 16, 16, 8, "cuda").requires_grad_(True) if a.bilateral_grid else None
+    gm, gv = (torch.zeros_like(grids), torch.zeros_like(grids)) if a.bilateral_grid else (None, None)
     ms = {n: [] for n in names}
     for it in range(a.warmup + a.iters):
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(7)]
         e[0].record()
         cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
         e[1].record()
         col, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, view, campos, K, W, H, background=bg, clamp_rgb=True, workspace=ws)
         e[2].record()
-        loss, _, _ = ops.photometric_loss(col, target, 0.2)
+        tv = None
+        if grids is not None:
+            col, tv = ops.bilagrid_slice(col, grids[it % 21:it % 21 + 1]), ops.bilagrid_tv(grids)
         e[3].record()
-        grads = torch.autograd.grad(loss, list(p.values()))
+        loss, _, _ = ops.photometric_loss(col, target, 0.2)
+        if tv is not None:
+            loss = loss + 10.0 * tv
         e[4].record()
+        grads = torch.autograd.grad(loss, list(p.values()) + ([grids] if grids is not None else []))
+        e[5].record()
         with torch.no_grad():
             for (k, t), gr in zip(p.items(), grads):
                 ops.adam_step(t, gr, m[k], v[k], lr=1e-3, step=it + 1, eps=1e-15, lr2=5e-5 if k == "sh" else None, period=25 if k == "sh" else 0)
-        e[5].record()
+            if grids is not None:
+                ops.adam_step(grids, grads[-1].contiguous(), gm, gv, lr=2e-3, step=it + 1, eps=1e-15)
+        e[6].record()
         torch.cuda.synchronize()
         if it >= a.warmup:
             for i, n in enumerate(names):
@@ -74,7 +88,7 @@ def main():
             tc.append(e[1].elapsed_time(e[2]))
     nbytes = sh.numel() * 28
     a_ms, c_ms = statistics.median(ta), statistics.median(tc)
-    print(json.dumps(dict(gaussians=U, size=W, step_ms=round(sum(med.values()), 3), **{n + "_ms": round(x, 3) for n, x in med.items()},
+    print(json.dumps(dict(gaussians=U, size=W, bilateral_grid=bool(a.bilateral_grid), step_ms=round(sum(med.values()), 3), **{n + "_ms": round(x, 3) for n, x in med.items()},
                           adam_sh_elements=sh.numel(), adam_sh_ms=round(a_ms, 3), adam_sh_GBps=round(nbytes / a_ms / 1e6, 1),
                           copy_same_bytes_ms=round(c_ms, 3), copy_GBps=round(nbytes / c_ms / 1e6, 1), adam_over_copy=round(a_ms / c_ms, 2))))
 

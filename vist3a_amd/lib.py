@@ -249,6 +249,23 @@ class DepthLossArgs(C.Structure):
     ]
 
 
+class BilagridSliceArgs(C.Structure):
+    _fields_ = [
+        ("rgb", C.c_void_p), ("grids", C.c_void_p),
+        ("N", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("GX", C.c_int), ("GY", C.c_int), ("L", C.c_int),
+    ]
+
+
+class BilagridTvArgs(C.Structure):
+    _fields_ = [
+        ("grids", C.c_void_p),
+        ("V", C.c_int), ("GX", C.c_int), ("GY", C.c_int), ("L", C.c_int),
+        ("out", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
 class AdamArgs(C.Structure):
     _fields_ = [
         ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
@@ -333,13 +350,18 @@ SYMBOLS = {
     "v3a_depth_loss_workspace_bytes": (C.c_long, [C.c_int] * 3),
     "v3a_depth_loss_forward": (C.c_int, [C.POINTER(DepthLossArgs), C.c_void_p]),
     "v3a_depth_loss_backward": (C.c_int, [C.POINTER(DepthLossArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v3a_bilagrid_slice_forward": (C.c_int, [C.POINTER(BilagridSliceArgs), C.c_void_p, C.c_void_p]),
+    "v3a_bilagrid_slice_backward": (C.c_int, [C.POINTER(BilagridSliceArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v3a_bilagrid_tv_workspace_bytes": (C.c_long, [C.c_int] * 4),
+    "v3a_bilagrid_tv_forward": (C.c_int, [C.POINTER(BilagridTvArgs), C.c_void_p]),
+    "v3a_bilagrid_tv_backward": (C.c_int, [C.POINTER(BilagridTvArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
     "v3a_splat_activate": (C.c_int, [C.c_void_p] * 3 + [C.c_long] + [C.c_void_p] * 3),
     "v3a_splat_activate_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),
     "v3a_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 27   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 28   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

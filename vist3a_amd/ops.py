@@ -1479,6 +1479,111 @@ def depth_loss(depth: torch.Tensor, alpha: torch.Tensor, depth_gt: torch.Tensor,
     return _DepthLoss.apply(depth, alpha, depth_gt, mask, float(scale))
 
 
+class _BilagridSlice(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rgb, grids):
+        N, H, W, _ = rgb.shape
+        _, Lz, GY, GX, _ = grids.shape
+        out = torch.empty_like(rgb)
+        args = L.BilagridSliceArgs(_ptr(rgb), _ptr(grids), N, H, W, GX, GY, Lz)
+        L.check(L.load().v3a_bilagrid_slice_forward(C.byref(args), _ptr(out), _stream()),
+                f"v3a_bilagrid_slice_forward (rgb {tuple(rgb.shape)}, grids {tuple(grids.shape)})")
+        ctx.save_for_backward(rgb, grids)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        rgb, grids = ctx.saved_tensors
+        N, H, W, _ = rgb.shape
+        _, Lz, GY, GX, _ = grids.shape
+        d_out = d_out.float().contiguous()
+        d_rgb = torch.empty_like(rgb) if ctx.needs_input_grad[0] else None
+        d_grids = torch.empty_like(grids) if ctx.needs_input_grad[1] else None
+        args = L.BilagridSliceArgs(_ptr(rgb), _ptr(grids), N, H, W, GX, GY, Lz)
+        L.check(L.load().v3a_bilagrid_slice_backward(C.byref(args), _ptr(d_out), _ptr(d_rgb), _ptr(d_grids), _stream()),
+                "v3a_bilagrid_slice_backward")
+        return d_rgb, d_grids
+
+
+def _bilagrid_check(grids: torch.Tensor, what: str) -> None:
+    if grids.dim() != 5 or grids.shape[-1] != 12:
+        raise ValueError(f"{what}: grids must be [V,L,GY,GX,12], got {tuple(grids.shape)}")
+    _f32_dev(grids, "grids")
+
+
+def bilagrid_slice(rgb: torch.Tensor, grids: torch.Tensor) -> torch.Tensor:
+    """The reference's bilateral-grid slice (lib_bilagrid.py::slice, one grid per image) on csrc/bilagrid.hip: `rgb` f32 [N,H,W,3]
+    as gs_render emits it, `grids` f32 [N,L,GY,GX,12] (coefficient 4c + k = row c, column k of the 3x4 matrix; GX, GY, L >= 2).
+    Pixel (i, j) samples its image's grid at ((j + 0.5) / W, (i + 0.5) / H, gray(rgb)) - trilinear, align_corners=True, border -
+    and the 3x4 affine matrix it gets is applied to its colour.  -> f32 [N,H,W,3], differentiable with respect to both inputs
+    (HIP backward, first order only; deterministic, no atomics)."""
+    if rgb.dim() != 4 or rgb.shape[-1] != 3:
+        raise ValueError(f"bilagrid_slice: rgb must be [N,H,W,3], got {tuple(rgb.shape)}")
+    _f32_dev(rgb, "rgb")
+    _bilagrid_check(grids, "bilagrid_slice")
+    if grids.shape[0] != rgb.shape[0]:
+        raise ValueError(f"bilagrid_slice: one grid per image: grids must have shape [{rgb.shape[0]},L,GY,GX,12], got {tuple(grids.shape)}")
+    return _BilagridSlice.apply(rgb, grids)
+
+
+class _BilagridTv(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, grids):
+        V, Lz, GY, GX, _ = grids.shape
+        lib = L.load()
+        need = lib.v3a_bilagrid_tv_workspace_bytes(V, GX, GY, Lz)
+        if need < 0:
+            L.check(int(need), f"v3a_bilagrid_tv_workspace_bytes (grids {tuple(grids.shape)})")
+        ws = torch.empty((int(need) + 7) // 8, device=grids.device, dtype=torch.float64)
+        out = torch.empty(1, device=grids.device, dtype=torch.float64)
+        args = L.BilagridTvArgs(_ptr(grids), V, GX, GY, Lz, _ptr(out), _ptr(ws), ws.numel() * 8)
+        L.check(lib.v3a_bilagrid_tv_forward(C.byref(args), _stream()), "v3a_bilagrid_tv_forward")
+        ctx.save_for_backward(grids)
+        return out[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_tv):
+        grids, = ctx.saved_tensors
+        V, Lz, GY, GX, _ = grids.shape
+        d_out = d_tv.to(torch.float64).reshape(1).contiguous()
+        d_grids = torch.empty_like(grids)
+        args = L.BilagridTvArgs(_ptr(grids), V, GX, GY, Lz, None, None, 0)
+        L.check(L.load().v3a_bilagrid_tv_backward(C.byref(args), _ptr(d_out), _ptr(d_grids), _stream()), "v3a_bilagrid_tv_backward")
+        return d_grids
+
+
+def bilagrid_tv(grids: torch.Tensor) -> torch.Tensor:
+    """lib_bilagrid.py::total_variation_loss of `grids` f32 [V,L,GY,GX,12] (csrc/bilagrid.hip): per axis L, GY, GX the sum of squared
+    forward differences over the number of differences, added and divided by V.  -> a float64 scalar on the device, differentiable
+    (HIP backward, first order only)."""
+    _bilagrid_check(grids, "bilagrid_tv")
+    return _BilagridTv.apply(grids)
+
+
+def bilagrid_identity(V: int, GX: int, GY: int, L: int, device) -> torch.Tensor:
+    """V identity grids f32 [V,L,GY,GX,12]: every vertex holds the 3x4 matrix [I | 0]"""
+    if V < 1 or min(GX, GY, L) < 2:
+        raise ValueError(f"bilagrid_identity: V >= 1 and GX, GY, L >= 2 required, got V={V}, (GX, GY, L)={(GX, GY, L)}")
+    eye = torch.tensor([1.0, 0, 0, 0, 0, 1.0, 0, 0, 0, 0, 1.0, 0], dtype=f32, device=device)
+    return eye.repeat(V, L, GY, GX, 1).contiguous()
+
+
+def bilagrid_from_reference(t: torch.Tensor) -> torch.Tensor:
+    """the reference's BilateralGrid.grids [V,12,L,GY,GX] -> this package's [V,L,GY,GX,12] (a copy)"""
+    if t.dim() != 5 or t.shape[1] != 12:
+        raise ValueError(f"bilagrid_from_reference: expected [V,12,L,GY,GX], got {tuple(t.shape)}")
+    return t.permute(0, 2, 3, 4, 1).contiguous()
+
+
+def bilagrid_to_reference(t: torch.Tensor) -> torch.Tensor:
+    """this package's [V,L,GY,GX,12] -> the reference's [V,12,L,GY,GX] (a copy)"""
+    if t.dim() != 5 or t.shape[-1] != 12:
+        raise ValueError(f"bilagrid_to_reference: expected [V,L,GY,GX,12], got {tuple(t.shape)}")
+    return t.permute(0, 4, 1, 2, 3).contiguous()
+
+
 class _SplatActivate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_scales, quats, logits):

@@ -10,6 +10,11 @@ ops.depth_loss with cfg.depth_loss) -> backward -> ops.adam_step per trained ten
 autograd graph.  Nothing in the loop reads a value back to the host (apart from the rasteriser's own intersection count); the
 per-step loss, L1, SSIM and, with cfg.depth_loss, the depth term stay in a device tensor.
 
+cfg.use_bilateral_grid adds the reference's per-view bilateral grids (:352-355, :697-710, :831-846, :916-923, :962-964;
+lib_bilagrid.py): the render goes through ops.bilagrid_slice with the view's grid before the photometric loss, the loss gains
+cfg.bilagrid_tv_lambda * ops.bilagrid_tv(all grids), and the grids [V,L,GY,GX,12] train with an Adam and a warm-up schedule of their
+own.  They absorb per-view exposure and white balance so that the scene does not; they stay in `splats` and are not exported.
+
 The harmonics stay ONE [U,3,K] tensor: the reference's sh0 / shN optimisers (rates lr_sh and lr_sh / 20) are one ops.adam_step with
 a period of K, which is the same arithmetic because Adam is elementwise."""
 from __future__ import annotations
@@ -42,6 +47,11 @@ class PostOptConfig:
     depth_loss: bool = False         # :358-360; the term itself :943-961, here on dense maps (ops.depth_loss)
     depth_lambda: float = 1e-2
     scene_scale: float = 1.0         # multiplies the depth term (:426, :960)
+    use_bilateral_grid: bool = False                        # :352-355
+    bilateral_grid_shape: Tuple[int, int, int] = (16, 16, 8)   # (X, Y, W = the guidance axis L), as the reference spells it
+    bilagrid_lr: float = 2e-3        # :707, times sqrt(batch_size) = 1
+    bilagrid_warmup_steps: int = 1000   # :839: LinearLR(0.01 -> 1) chained with the decay to 1 % over max_steps
+    bilagrid_tv_lambda: float = 10.0    # :963
     # ours
     params: Tuple[str, ...] = ("means", "scales", "quats", "opacities", "sh0", "shN")
     seed: int = 0
@@ -56,6 +66,25 @@ class PostOptConfig:
         if names & {"sh0", "shN"}:
             names = (names - {"sh0", "shN"}) | {"sh"}
         return tuple(n for n in PARAM_NAMES if n in names)
+
+    def check_bilagrid(self) -> None:
+        if not self.use_bilateral_grid:
+            return
+        shape = tuple(self.bilateral_grid_shape)
+        if len(shape) != 3 or any(not isinstance(n, int) or isinstance(n, bool) or n < 2 for n in shape):
+            raise ValueError(f"PostOptConfig.bilateral_grid_shape must be three integers (X, Y, W) >= 2, got {self.bilateral_grid_shape!r}")
+        if not isinstance(self.bilagrid_warmup_steps, int) or self.bilagrid_warmup_steps < 1:
+            raise ValueError(f"PostOptConfig.bilagrid_warmup_steps must be a positive integer, got {self.bilagrid_warmup_steps!r}")
+        if not self.bilagrid_lr > 0 or not self.bilagrid_tv_lambda >= 0:
+            raise ValueError(f"PostOptConfig.bilagrid_lr must be positive and bilagrid_tv_lambda non-negative, got {self.bilagrid_lr!r} "
+                             f"and {self.bilagrid_tv_lambda!r}")
+
+
+def bilagrid_learning_rate(cfg: PostOptConfig, s: int) -> float:
+    """The grid Adam's rate at the step with `s` earlier steps: the closed form of the reference's ChainedScheduler(LinearLR(0.01,
+    warmup), ExponentialLR(0.01 ** (1 / max_steps))) (:831-846)."""
+    w = cfg.bilagrid_warmup_steps
+    return cfg.bilagrid_lr * (0.01 + 0.99 * min(s, w) / w) * (0.01 ** (s / cfg.max_steps))
 
 
 def view_order(n_views: int, steps: int, seed: int) -> list:
@@ -72,9 +101,10 @@ def _single(gaussians: Gaussians) -> None:
         raise ValueError(f"post-optimisation takes one scene (batch dimension 1), got means of shape {tuple(gaussians.means.shape)}")
 
 
-def create_splats(gaussians: Gaussians, cfg: PostOptConfig) -> dict:
+def create_splats(gaussians: Gaussians, cfg: PostOptConfig, n_views: Optional[int] = None) -> dict:
     """-> {"params": {name: f32 tensor}, "m": {...}, "v": {...}, "step": 0, "keep": bool [U] (the rows kept)}.  scales are stored as
-    logs, opacities as logits (clamped to 1 - 1e-6 so that the logit is finite), quaternions as they come (xyzw, as `Gaussians` keeps them)."""
+    logs, opacities as logits (clamped to 1 - 1e-6 so that the logit is finite), quaternions as they come (xyzw, as `Gaussians` keeps them).
+    With cfg.use_bilateral_grid and `n_views`, also "bil_grids" (identity, f32 [n_views,L,GY,GX,12]) and its moments "bil_m", "bil_v"."""
     _single(gaussians)
     if not gaussians.means.is_cuda:
         raise ValueError("post-optimisation runs on the device (the HIP path has no CPU fallback)")
@@ -86,7 +116,18 @@ def create_splats(gaussians: Gaussians, cfg: PostOptConfig) -> dict:
                  opacities=torch.logit(op[keep].clamp(max=1 - 1e-6)).contiguous(), sh=sel(gaussians.harmonics))
     if p["means"].shape[0] == 0:
         raise ValueError(f"no Gaussian has an opacity above min_opacity = {cfg.min_opacity}")
-    return dict(params=p, m={k: torch.zeros_like(t) for k, t in p.items()}, v={k: torch.zeros_like(t) for k, t in p.items()}, step=0, keep=keep)
+    splats = dict(params=p, m={k: torch.zeros_like(t) for k, t in p.items()}, v={k: torch.zeros_like(t) for k, t in p.items()}, step=0, keep=keep)
+    if cfg.use_bilateral_grid and n_views is not None:
+        add_bilateral_grids(splats, cfg, n_views)
+    return splats
+
+
+def add_bilateral_grids(splats: dict, cfg: PostOptConfig, n_views: int) -> None:
+    """splats["bil_grids"]: one identity grid per training view, with its Adam moments (the reference's BilateralGrid(len(trainset), ...))"""
+    cfg.check_bilagrid()
+    GX, GY, L = cfg.bilateral_grid_shape
+    g = ops.bilagrid_identity(n_views, GX, GY, L, splats["params"]["means"].device)
+    splats.update(bil_grids=g, bil_m=torch.zeros_like(g), bil_v=torch.zeros_like(g))
 
 
 def _cameras(extrinsics, intrinsics, W, H, dev):
@@ -116,12 +157,15 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     [V,4,4]) with `intrinsics` (normalised [V,3,3]) - the decoder's conventions.  `steps` (default cfg.max_steps) steps of one view
     each; the means' learning-rate schedule always spans cfg.max_steps.  -> (Gaussians, log): the refined scene (rows at or below
     cfg.min_opacity dropped) and a float64 device tensor of per-step (loss, l1, ssim), [steps,3], or with cfg.depth_loss
-    (loss, l1, ssim, depth_term), [steps,4]: loss is the total, depth_term the unweighted term.
+    (loss, l1, ssim, depth_term), [steps,4]: loss is the total, depth_term the unweighted term.  With cfg.use_bilateral_grid a
+    last column holds the unweighted total variation of the grids; the returned Gaussians are the raw scene (no grid applied) and
+    the trained grids stay in `splats["bil_grids"]` (pass `splats` to keep them).
 
     With cfg.depth_loss the step's loss is photometric + cfg.depth_lambda * ops.depth_loss(rendered depth, alpha, depths[j],
     depth_masks[j], cfg.scene_scale): `depths` f32 [V,H,W] on the device are z along the camera axis in the units of `extrinsics`,
     `depth_masks` bool / uint8 [V,H,W] (or None: every pixel with a positive finite depth).  Without cfg.depth_loss `depths` is ignored."""
     cfg = cfg or PostOptConfig()
+    cfg.check_bilagrid()
     _single(gaussians)
     for t, n in ((extrinsics, "extrinsics"), (intrinsics, "intrinsics")):
         if t.requires_grad:
@@ -147,24 +191,36 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
         raise ValueError("images must be on the device (the HIP path has no CPU fallback)")
     steps = cfg.max_steps if steps is None else int(steps)
     trained = cfg.trained()
-    splats = splats if splats is not None else create_splats(gaussians, cfg)
+    splats = splats if splats is not None else create_splats(gaussians, cfg, V)
     p, m, v = splats["params"], splats["m"], splats["v"]
+    bil = cfg.use_bilateral_grid
+    if bil:
+        if "bil_grids" not in splats:
+            add_bilateral_grids(splats, cfg, V)
+        GX, GY, Lz = cfg.bilateral_grid_shape
+        if tuple(splats["bil_grids"].shape) != (V, Lz, GY, GX, 12):
+            raise ValueError(f"splats['bil_grids'] has shape {tuple(splats['bil_grids'].shape)}, the {V} views and "
+                             f"cfg.bilateral_grid_shape want {(V, Lz, GY, GX, 12)}")
     dev = p["means"].device
     Ksh = p["sh"].shape[-1]
     sh_degree = isqrt(Ksh) - 1
     view, campos, Kpix = _cameras(extrinsics, intrinsics, W, H, dev)
     images = images.contiguous()
     background = torch.zeros(3, device=dev, dtype=torch.float32)
-    log = torch.zeros(steps, 4 if cfg.depth_loss else 3, device=dev, dtype=torch.float64)
+    log = torch.zeros(steps, 3 + int(cfg.depth_loss) + int(bil), device=dev, dtype=torch.float64)
     lrs = dict(means=cfg.lr_means, scales=cfg.lr_scales, quats=cfg.lr_quats, opacities=cfg.lr_opacities, sh=cfg.lr_sh)
     decay = 0.01 ** (1.0 / cfg.max_steps)
     ws = ops.GsWorkspace()
     leaves = [p[n].requires_grad_(True) for n in trained]
+    if bil:
+        leaves.append(splats["bil_grids"].requires_grad_(True))
     try:
         for i, j in enumerate(view_order(V, steps, cfg.seed)):
             cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
             color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
                                         sh_degree=sh_degree, sh_layout=1, background=background, clamp_rgb=True, workspace=ws)
+            if bil:
+                color = ops.bilagrid_slice(color, splats["bil_grids"][j:j + 1])
             loss, l1, ssim = ops.photometric_loss(color, images[j:j + 1], cfg.ssim_lambda)
             if cfg.depth_loss:
                 dterm, _ = ops.depth_loss(depth, alpha, depths[j:j + 1], None if depth_masks is None else depth_masks[j:j + 1], cfg.scene_scale)
@@ -172,6 +228,10 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
                 rec = [loss.detach(), l1.detach(), ssim.detach(), dterm.detach()]
             else:
                 rec = [loss.detach(), l1.detach(), ssim.detach()]
+            if bil:
+                tv = ops.bilagrid_tv(splats["bil_grids"])
+                loss = loss + cfg.bilagrid_tv_lambda * tv
+                rec = [loss.detach()] + rec[1:] + [tv.detach()]
             grads = torch.autograd.grad(loss, leaves)
             log[i].copy_(torch.stack(rec))
             t = splats["step"] + 1
@@ -181,8 +241,13 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
                     sh = n == "sh"
                     ops.adam_step(p[n], g.contiguous(), m[n], v[n], lr=lr, step=t, betas=cfg.betas, eps=cfg.eps,
                                   lr2=lr / 20 if sh else None, period=Ksh if sh and Ksh > 1 else 0)
+                if bil:   # every view's grid moves each step through the TV term, as in the reference
+                    ops.adam_step(splats["bil_grids"], grads[-1].contiguous(), splats["bil_m"], splats["bil_v"],
+                                  lr=bilagrid_learning_rate(cfg, t - 1), step=t, betas=cfg.betas, eps=1e-15, period=0)
             splats["step"] = t
     finally:
         for n in trained:
             p[n].requires_grad_(False)
+        if bil:
+            splats["bil_grids"].requires_grad_(False)
     return splats_to_gaussians(splats), log

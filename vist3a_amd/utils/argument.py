@@ -47,6 +47,9 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
                    help="weight of the post-optimisation's depth term (the reference's depth_loss / depth_lambda, there 1e-2): an L1 in "
                         "disparity between the rendered expected depth and the depth head's map of each view, on its confident pixels; "
                         "0 = off")
+    g.add_argument("--post_opt_bilateral_grid", action="store_true",
+                   help="post-optimisation with one bilateral grid per view (the reference's use_bilateral_grid): the grids absorb the "
+                        "frames' exposure and white-balance drift instead of the scene; they are not exported")
     return p
 
 
