@@ -9,6 +9,21 @@
  *   - `stream` is a hipStream_t passed as void*; calls are stream-ordered, re-entrant, allocate nothing;
  *   - return 0 on success, negative V3A_ERR_* otherwise; never throws;
  *   - bf16 tensors are raw uint16 storage (round-to-nearest-even, same as torch.bfloat16).
+ *
+ * MEMORY CONTRACT.  An entry point reads and writes only the [rows, cols] region of each operand and the first
+ * `workspace_bytes` bytes of its workspace.  Row strides (ld*), batch / segment strides and row scatters (out_row_*) say where
+ * the rows lie, never how much of one may be touched: columns cols .. ld, rows the scatter skips, the gap between two batch
+ * items or two slabs, and everything before the first and after the last element belong to the caller - typically to the
+ * neighbouring operand of a fused buffer - and are neither loaded (their contents, NaN included, cannot reach a result) nor
+ * stored.  In-place operands (residual aliasing C, y aliasing x, v3a_qknorm_rope2d, v3a_adam_step's p / m / v) follow the same
+ * rule for their padding.  Where an entry point by design owns MORE than the region, its comment states the exact extent:
+ *   - v3a_attn_args.vt / v3a_attn_fp8_args.vt: every V^T row is READ up to the next multiple of 64 keys past each batch item's
+ *     Nk; the values there must be finite and do not reach the result; nothing beyond is read (with kv_seg a segment is a
+ *     whole number of 64-key tiles - kv_seg % 64 == 0, Nk % kv_seg == 0 - so exactly the segment is read);
+ *   - v3a_xattn_probs_args.p: the region is [B * Nq, H * Lkp]; columns Nk <= j < Lkp of every head are WRITTEN (zeros);
+ *   - packed convolution weights (w [Cout][Kpad], ktab [Kpad / 8], w_halo): read in full, padding chunks included.
+ * tests/test_guard_bands_gpu.py holds the entry points to this: every tensor carved out of an all-0xFF arena with guard bands,
+ * results bit-equal to those on tight tensors, guard bytes and inputs unchanged.
  */
 #ifndef VIST3A_HIP_H
 #define VIST3A_HIP_H

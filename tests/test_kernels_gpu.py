@@ -20,6 +20,21 @@ bf16, f32 = torch.bfloat16, torch.float32
 G = Path(__file__).parent / "golden"
 
 
+# gates of the tests below, named so that tests/test_guard_bands_gpu.py applies the SAME bars to its ragged shapes (values unchanged)
+TOL_GEMM = 1.2e-4            # bf16 GEMM / same rounding points: measured <= 5.5e-5 (profiles/r2/parity.json)
+TOL_GEMM_ACT = 1.5e-3        # erf / tanh GELU, SiLU: the device transcendental differs from torch's by an ulp before the bf16 rounding
+TOL_GEMM_SPLIT_K = 4e-3      # bf16 partials: ~sqrt(2) x one output rounding (2.2e-3)
+TOL_GEMM_FP8 = 1.2e-3        # e4m3 GEMM vs its emulation: bf16 output rounding flips
+TOL_ROW_SUMSQ = 1e-5         # row_sumsq by-product vs the squares of the stored output summed in fp32 (max relative)
+TOL_ATTN_SPLIT_EXACT = 5e-3  # key-split flash attention vs fp32 softmax attention
+TOL_ATTN_FP8_EMU = 3e-3      # e4m3 attention vs its emulation
+TOL_XATTN = 3e-3             # xattn_probs vs fp32 softmax: the bf16 rounding of P itself
+TOL_LN_ADALN = 4e-5          # AdaLN layernorm, bf16 out: measured 1.5e-5
+TOL_LN_F32 = 1e-5            # affine layernorm, fp32 in / out
+TOL_RMSNORM_ROPE = 6e-5      # measured 2.2e-5
+TOL_CONV = 1.5e-4            # implicit-GEMM / halo-tile convolution vs torch conv3d on the same bf16 operands: measured <= 6.2e-5
+
+
 def relerr(a, b):
     a, b = a.float(), b.float()
     return ((a - b).norm() / b.norm().clamp_min(1e-20)).item()
@@ -92,7 +107,7 @@ def test_gemm_production_shapes_every_tile(hip_lib, parity, name, M, N, K, opt):
         r = relerr(out, ref)
         worst = max(worst, r)
         parity("gemm_production", shape=name, M=M, N=N, K=K, tile=tn, auto=(t == auto), rel_vs_fp32=r)
-        assert math.isfinite(r) and r < 1.2e-4, (tn, r)   # measured <= 5.5e-5 (profiles/r2/parity.json)
+        assert math.isfinite(r) and r < TOL_GEMM, (tn, r)   # measured <= 5.5e-5 (profiles/r2/parity.json)
         if first is None:
             first = out
         else:
@@ -138,7 +153,7 @@ def test_gemm_epilogue_flags_every_tile(hip_lib, parity):
             r = relerr(out, ref)
             parity("gemm_flags", case={k: v for k, v in c.items()}, tile=tn, rel_vs_fp32=r)
             # erf/tanh GELU: device transcendental vs torch's differ by an ulp before the bf16 rounding (measured <= 6e-4)
-            assert math.isfinite(r) and r < (1.5e-3 if kw["act"] in (L.ACT_GELU_ERF, L.ACT_GELU_TANH, L.ACT_SILU) else 1.2e-4), (tn, c, r)
+            assert math.isfinite(r) and r < (TOL_GEMM_ACT if kw["act"] in (L.ACT_GELU_ERF, L.ACT_GELU_TANH, L.ACT_SILU) else TOL_GEMM), (tn, c, r)
             if first is None:
                 first = out
             else:
@@ -168,7 +183,7 @@ def test_gemm_split_k_matches_unsplit(hip_lib, parity, M, N, K, S, opt):
     r, r1 = relerr(s1, ref), relerr(s1, one)
     parity("gemm_split_k", M=M, N=N, K=K, S=S, rel_vs_fp32=r, rel_vs_one_launch=r1)
     assert torch.equal(s1, s2)
-    assert r < 4e-3 and r1 < 4e-3, (r, r1)   # bf16 partials: ~sqrt(2) x one output rounding (2.2e-3)
+    assert r < TOL_GEMM_SPLIT_K and r1 < TOL_GEMM_SPLIT_K, (r, r1)   # bf16 partials: ~sqrt(2) x one output rounding (2.2e-3)
     with pytest.raises(RuntimeError):
         ops.gemm(a[:, :192], w[:, :192], None, split_k=2)   # K % (64 * split_k) != 0
 
@@ -284,7 +299,7 @@ def test_attention_key_split_matches_unsplit_and_fp32(hip_lib, parity, B, H, Nq,
     r, r1 = relerr(a, ref), relerr(a, one)
     parity("attention_hd128_key_split", B=B, H=H, Nq=Nq, Nk=Nk, S=S, rel_vs_fp32=r, rel_vs_unsplit=r1)
     assert torch.equal(a, b)
-    assert r < 5e-3 and r1 < 6e-3, (r, r1)   # two bf16-P flash results differ by ~sqrt(2) x their own 2.3e-3
+    assert r < TOL_ATTN_SPLIT_EXACT and r1 < 6e-3, (r, r1)   # two bf16-P flash results differ by ~sqrt(2) x their own 2.3e-3
 
 
 def test_attention_hd128_cross_attention_merged_padding_keys(hip_lib, parity):
@@ -379,7 +394,7 @@ def test_conv_variants_match_torch_conv3d(hip_lib, parity, case):
     r = relerr(y[..., :Cout], refcl)
     parity("conv_variant", name=name, rel_vs_fp32=r)
     assert tuple(y.shape[:3]) == tuple(ref.shape[2:])
-    assert r < 1.5e-4, (name, r)   # measured <= 6.2e-5
+    assert r < TOL_CONV, (name, r)   # measured <= 6.2e-5
     if cw.CoutP != Cout:
         assert (y[..., Cout:].float() - res[..., Cout:].float()).abs().max() == 0
 
@@ -424,11 +439,11 @@ def test_conv_halo_tile_kernel_matches_torch_and_implicit_gemm(hip_lib, parity, 
     r, ri = relerr(y, refcl), relerr(y, yi)
     parity("conv_halo", name=name, rel_vs_fp32=r, rel_vs_implicit_gemm=ri)
     assert tuple(y.shape) == (T, H, W, Cout) and torch.equal(y, y2)
-    assert r < 1.5e-4 and ri < 1.5e-4, (name, r, ri)
+    assert r < TOL_CONV and ri < TOL_CONV, (name, r, ri)
     # SiLU-free activation path of the epilogue + no residual (conv1 of a residual block feeds rownorm, conv_out has neither)
     y3 = ops.conv(xcl, cw, pad=pad, ups2=ups2, tile=-2)
     r3 = relerr(y3, ref[0].permute(1, 2, 3, 0).to(bf16))
-    assert r3 < 1.5e-4, (name, r3)
+    assert r3 < TOL_CONV, (name, r3)
 
 
 def test_conv_halo_dispatch_rules(hip_lib):
@@ -548,12 +563,12 @@ def test_norm_kernels_production_shapes(hip_lib, parity):
         idx = torch.arange(M, device=dev) // (rpb or M)
         r = relerr(y, (ln * (1 + sc[idx]) + sh[idx]).to(bf16))
         parity("layernorm_adaln", M=M, d=d, rel_vs_fp32=r)
-        assert r < 4e-5, r   # measured 1.5e-5 (bf16 output rounding flips)
+        assert r < TOL_LN_ADALN, r   # measured 1.5e-5 (bf16 output rounding flips)
         xf = x.float() * 1.37
         y = ops.layernorm(xf, weight=w, bias=b, eps=1e-5, out_dtype=f32)
         r = relerr(y, torch.nn.functional.layer_norm(xf, (d,), w, b, eps=1e-5))
         parity("layernorm_affine_f32", M=M, d=d, rel_vs_fp32=r)
-        assert r < 1e-5, r
+        assert r < TOL_LN_F32, r
     for (B, N, H, hd) in [(2, 4096, 12, 128), (1, 300, 3, 128)]:
         d, M = H * hd, B * N
         x = torch.randn(M, d, device=dev, generator=g).to(bf16)
@@ -567,7 +582,7 @@ def test_norm_kernels_production_shapes(hip_lib, parity):
         fc = torch.polar(torch.ones_like(ang), ang)[None, :, None, :]
         r = relerr(y, torch.view_as_real(nc * fc).reshape(M, d).to(bf16))
         parity("rmsnorm_rope", B=B, N=N, rel_vs_fp32=r)
-        assert r < 6e-5, r   # measured 2.2e-5
+        assert r < TOL_RMSNORM_ROPE, r   # measured 2.2e-5
         # q | k of the fused projection in ONE launch (weight2) == the two separate launches
         qk = torch.randn(M, 2 * d, device=dev, generator=g).to(bf16)
         w2 = torch.randn(d, device=dev, generator=g)
@@ -650,7 +665,7 @@ def test_attention_fp8_matches_e4m3_emulation(hip_lib, parity, B, H, Nq, Nk):
     r_emu, r_exact = relerr(out, emu), relerr(out, exact.transpose(1, 2))
     parity("attention_fp8", B=B, H=H, Nq=Nq, Nk=Nk, rel_vs_e4m3_emulation=r_emu, rel_vs_exact_fp32=r_exact)
     print(f"fp8 attention: rel vs e4m3 emulation {r_emu:.2e}, vs exact fp32 {r_exact:.2e}")
-    assert r_emu < 3e-3, r_emu          # bf16 output rounding + exp2 ulp flips at e4m3 rounding boundaries of P
+    assert r_emu < TOL_ATTN_FP8_EMU, r_emu          # bf16 output rounding + exp2 ulp flips at e4m3 rounding boundaries of P
     assert r_exact < 6e-2, r_exact      # what e4m3 operands cost (3 mantissa bits)
 
 
@@ -775,7 +790,7 @@ def test_gemm_fp8_every_tile_matches_e4m3_emulation(hip_lib, parity, name, M, N,
     quant_cost = relerr((qa @ qw.T) * (sa[:, None] * sw[None, :]), exact)
     parity(f"gemm_fp8_{name}", M=M, N=N, K=K, rel_vs_e4m3_emulation=worst, rel_e4m3_operands_vs_bf16_operands=quant_cost)
     assert all(torch.equal(o, first) for o in outs.values()) and torch.equal(auto, first)
-    assert worst < 1.2e-3, worst            # bf16 output rounding flips (fp32 accumulation order differs from torch's)
+    assert worst < TOL_GEMM_FP8, worst            # bf16 output rounding flips (fp32 accumulation order differs from torch's)
     assert quant_cost < 5e-2, quant_cost    # what 3 mantissa bits on both operands cost
 
 
@@ -838,7 +853,7 @@ def test_gemm_row_sumsq_by_product_is_tile_independent(hip_lib):
         if ref_sq is None:
             ref_sq, ref_out = sq, out
             want = out.float().view(M, N // 32, 32).pow(2).sum(-1)
-            assert ((sq - want).abs() / want).max().item() < 1e-5
+            assert ((sq - want).abs() / want).max().item() < TOL_ROW_SUMSQ
         assert torch.equal(out, ref_out) and torch.equal(sq, ref_sq), names[t]
     assert torch.equal(ops.gemm(a, w, bias), ref_out)     # and the by-product does not disturb the output
     # the statistics describe bf16(acc + bias) only: any epilogue stage behind it is refused, not silently mis-described
@@ -898,8 +913,8 @@ def test_xattn_probs_matches_fp32_softmax(hip_lib, parity, name, B, H, Nq, Nk, L
     got2 = out2[:, :Kp].float().view(B, Nq, H, Lkp).permute(0, 2, 1, 3)
     r2 = ((got2[..., :Nk] - ref2).norm() / ref2.norm()).item()
     parity("xattn_probs", name=name, rel_vs_fp32=r, correctly_rounded_share=exact, max_rowsum_error=rowsum, rel_vs_fp32_folded_q_norm=r2)
-    assert r < 3e-3 and exact > 0.999 and rowsum < 5e-3, (r, exact, rowsum)   # measured: rel 1.3-1.7e-3 = the bf16 rounding of P itself; 99.99 % of the elements ARE the correctly rounded fp32 value
-    assert r2 < 3e-3 and (got2[..., Nk:] == 0).all(), r2
+    assert r < TOL_XATTN and exact > 0.999 and rowsum < 5e-3, (r, exact, rowsum)   # measured: rel 1.3-1.7e-3 = the bf16 rounding of P itself; 99.99 % of the elements ARE the correctly rounded fp32 value
+    assert r2 < TOL_XATTN and (got2[..., Nk:] == 0).all(), r2
 
 
 def test_gemm_batched_operands_equal_separate_launches(hip_lib):

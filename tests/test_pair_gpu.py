@@ -9,6 +9,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 f32, f64, bf16 = torch.float32, torch.float64, torch.bfloat16
+TOL_SPLIT = 2e-5     # the split-bf16 kernels vs float64 (named so that tests/test_guard_bands_gpu.py applies the same bar; value unchanged)
 
 
 def _rel(a, b):
@@ -99,7 +100,7 @@ def test_conv_split_vs_float64(hip_lib, parity, case):
         full = ref.permute(0, 2, 3, 1)                   # [T,H,W,Cout]
         for dy in range(4):
             e = _rel(y[:, dy::4], full)
-            assert e < 2e-5, (case, dy, e)
+            assert e < TOL_SPLIT, (case, dy, e)
         parity(f"conv_split_{case}", rel=e)
         return
     y = ops.conv_split(xp.cuda(), cw, **kw)
@@ -107,7 +108,7 @@ def test_conv_split_vs_float64(hip_lib, parity, case):
     e, e32 = _rel(y, ref), _rel(plain if ref_post is None else ref_post(plain), ref)
     parity(f"conv_split_{case}", rel=e, torch_fp32_rel=e32)
     print(f"conv_split {case}: {e:.2e} vs float64 (plain fp32 torch: {e32:.2e})")
-    assert e < 2e-5, (case, e)      # measured <= 6e-6 on MI355X
+    assert e < TOL_SPLIT, (case, e)      # measured <= 6e-6 on MI355X
 
 
 def test_conv_split_every_tile(hip_lib):
@@ -127,7 +128,7 @@ def test_conv_split_every_tile(hip_lib):
         except RuntimeError:
             continue     # ping-pong tiles have no convolution form
         e = _rel(y.cpu().permute(0, 3, 1, 2), ref)
-        assert e < 2e-5, (tile, e)
+        assert e < TOL_SPLIT, (tile, e)
         done += 1
     assert done >= 10
 
@@ -200,7 +201,7 @@ def test_conv_split_halo_form_vs_float64(hip_lib, parity, cout, cin, H, W):
     e, ei, d = _rel(yh, ref), _rel(yi, ref), _rel(yh, yi)
     parity("conv_split_halo", cout=cout, cin=cin, rel=e, implicit_rel=ei, halo_vs_implicit=d)
     print(f"halo split {cin}->{cout} {H}x{W}: {e:.2e} vs float64 (implicit form {ei:.2e}, between them {d:.2e})")
-    assert e < 2e-5 and d < 2e-5
+    assert e < TOL_SPLIT and d < 2e-5
     # f32 output + f32 table residual through the same kernel
     tab = torch.randn(H * W, cout, generator=g)
     y32 = ops.conv_split(xp.cuda(), cw, tile=-2, pad=(0, 1, 1), residual=tab.cuda(), res_row_mod=H * W, out_f32=True).cpu().permute(0, 3, 1, 2)

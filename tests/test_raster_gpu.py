@@ -48,8 +48,13 @@ def test_projection_matches_oracle(hip_lib, U, W, H):
     means, cov, sh, op = _scene(U, 1)
     view, K = _camera(W, H, 70.0)
     pr = _project_gpu(ops, means, cov, sh, view, K, W, H)
+    check_projection(pr, means, cov, sh, view, K, W, H)
+
+
+def check_projection(pr, means, cov, sh, view, K, W, H, sh_degree=4):
+    """one camera's gs_project output against the oracle, under the bars of the module docstring (shared with tests/test_guard_bands_gpu.py)"""
     ref = G.project(means, cov, view, K, W, H)
-    col = G.sh_colors(means, torch.linalg.inv(view)[:3, 3], sh.permute(0, 2, 1), 4)
+    col = G.sh_colors(means, torch.linalg.inv(view)[:3, 3], sh.permute(0, 2, 1), sh_degree)
     rg, rr = pr["radii"].cpu(), ref["radii"]
     diff = (rg != rr)
     assert int((rg - rr).abs().max()) <= 1 and diff.float().mean().item() < 2e-3
