@@ -38,7 +38,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 27) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 29) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -703,6 +703,48 @@ typedef struct {
 long v3a_bilagrid_tv_workspace_bytes(int V, int GX, int GY, int L);   /* V3A_ERR_SHAPE for a size under 2 or too large */
 int v3a_bilagrid_tv_forward(const v3a_bilagrid_tv_args* a, void* stream);
 int v3a_bilagrid_tv_backward(const v3a_bilagrid_tv_args* a, const double* d_out, float* d_grids, void* stream);
+
+/* Colour correction before PSNR (csrc/color_correct.hip; lib_bilagrid.py:56-126 color_correct, the cc_psnr of simple_trainer.py::eval).
+ * img, ref, out: f32 [N,H,W,3], a pixel's three channels contiguous, row stride ld_* and image stride *_stride in ELEMENTS
+ * (ld >= 3 W, stride >= (H - 1) ld + 3 W for N > 1: V3A_ERR_SHAPE otherwise); only the [H, 3 W] region of each image is read or
+ * written.  Per image, num_iters (1 .. 16) rounds on the estimate x (= img at first, not clipped): features
+ * (r^2, rg, rb, g^2, gb, b^2, r, g, b, 1) of x; for each output channel c the least-squares fit of the 10 coefficients to ref[c]
+ * over the pixels with img[c], x[c] and ref[c] all in [eps, 1 - eps]; x = clip(features . warp, 0, 1).  fp64 after the f32 loads
+ * (sums, the 10 x 10 normal equations solved on the device, the update); out is rounded to f32 once and every element of it is
+ * written exactly once.  sse[n] = sum over the image of (out - ref)^2 in fp64, of the stored f32 values.
+ * status[n][c] (a deviation: the reference asserts or is undefined on such a channel): bit 0 = in some round fewer than 10 pixels
+ * were usable, bit 1 = a pivot of the elimination was <= 1e-12 times its diagonal entry of the Gram matrix (or the solution was
+ * not finite); in such a round the channel keeps the identity warp (x[c] passes through, clipped).  0 = every round was solved.
+ * 2 num_iters + 2 launches, fixed-order reductions, no atomics: bit-identical run to run, and an image's result does not depend
+ * on the other images of the call.  0 <= eps < 0.5 (V3A_ERR_ARG otherwise); float pointers 4-byte, sse 8-byte aligned (V3A_ERR_ARG). */
+typedef struct {
+  const float* img; const float* ref;
+  float* out;
+  int N, H, W;
+  int num_iters;
+  long ld_img, ld_ref, ld_out;                /* row strides, elements */
+  long img_stride, ref_stride, out_stride;    /* image strides, elements (unused for N = 1) */
+  double eps;
+  double* sse;                                /* out [N] */
+  int32_t* status;                            /* out [N,3] */
+  void* workspace; long workspace_bytes;      /* v3a_color_correct_workspace_bytes(N, H, W, num_iters), 8-byte aligned */
+} v3a_color_correct_args;
+long v3a_color_correct_workspace_bytes(int N, int H, int W, int num_iters);   /* V3A_ERR_SHAPE for a size the fit rejects */
+int v3a_color_correct(const v3a_color_correct_args* a, void* stream);
+
+/* Plain per-image mean squared error of two f32 images [N,H,W,C] (csrc/color_correct.hip), rows of W C contiguous elements at
+ * row stride ld_*, images at *_stride (elements, as above): mse[n] = sum (a - b)^2 / (H W C), the difference and the sum in fp64,
+ * workgroup partials reduced in a fixed order (two launches, no atomics).  PSNR = -10 log10(mse) is the caller's. */
+typedef struct {
+  const float* a; const float* b;
+  int N, H, W, C;
+  long ld_a, ld_b;
+  long a_stride, b_stride;
+  double* mse;                                /* out [N] */
+  void* workspace; long workspace_bytes;      /* v3a_image_mse_workspace_bytes(N, H, W, C), 8-byte aligned */
+} v3a_image_mse_args;
+long v3a_image_mse_workspace_bytes(int N, int H, int W, int C);   /* V3A_ERR_SHAPE for a non-positive or too large size */
+int v3a_image_mse(const v3a_image_mse_args* a, void* stream);
 
 /* Splat activation (csrc/post_opt.hip), one thread per Gaussian: log-scales [U,3], raw quaternions [U,4] (xyzw, any length),
  * opacity logits [U] -> covariances [U,3,3] = R diag(exp(log_scale))^2 R^T with v3a_gaussian_adapter's quaternion order,

@@ -8,6 +8,7 @@ or OpenCV is importable; in this image neither exists and the same frames are wr
 One process per GPU; prompts are strided over ranks (no inter-GPU traffic), exactly like the reference (:53-62)."""
 from __future__ import annotations
 
+import json
 import os
 import sys
 import zlib
@@ -63,9 +64,11 @@ def build_text_encoder(args, device):
     return make_pipeline_text_encoder(UMT5TextEncoder(UMT5Config(), sd, device=device), AutoTokenizer.from_pretrained(tk))
 
 
-def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False):
+def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False, eval_every=0, lpips=None):
+    """-> (refined Gaussians, stats or None).  With eval_every = K > 0 the views with index % K == 0 are held out of the loop and
+    scored before and after it: stats = {"before": {...}, "after": {...}, "held_out": [...]} (vist3a_amd.post_opt.evaluate_views)."""
     from vist3a_amd import ops
-    from vist3a_amd.post_opt import PostOptConfig, post_optimize
+    from vist3a_amd.post_opt import PostOptConfig, evaluate_views, post_optimize, train_views
     with torch.no_grad():
         ff = ops.bilinear_cl(clip_cl, (res, res), align_corners=False)          # what Text23DGS.generate fed the reconstruction
         frames = ((ff[..., :3].float() + 1) / 2).clamp(0, 1).contiguous()       # [V,res,res,3] in [0,1]
@@ -81,8 +84,19 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
         cfg = PostOptConfig(depth_loss=True, depth_lambda=float(depth_lambda))
         extra = dict(depths=depths, depth_masks=masks)
     cfg.use_bilateral_grid = bool(bilateral_grid)
-    g, _ = post_optimize(gaussians, frames, pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach(), cfg, steps=steps, **extra)
-    return g
+    cfg.test_every = int(eval_every)
+    ext, intr = pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach()
+    stats = None
+    if cfg.test_every > 0:
+        train = set(train_views(frames.shape[0], cfg.test_every))      # raises when K leaves no view to train on
+        held = [i for i in range(frames.shape[0]) if i not in train]
+        score = lambda gs: evaluate_views(gs, frames[held].contiguous(), ext[held], intr[held], color_correct=cfg.use_bilateral_grid,
+                                          lpips=lpips)
+        stats = dict(before=score(gaussians), held_out=held)
+    g, _ = post_optimize(gaussians, frames, ext, intr, cfg, steps=steps, **extra)
+    if stats is not None:
+        stats = dict(before=stats["before"], after=score(g), held_out=stats["held_out"])
+    return g, stats
 
 
 def main(args):
@@ -105,6 +119,14 @@ def main(args):
         scene.pipe.plan = DenoisePlan.from_dist()
         stitched.recon_group = scene.pipe.plan.world      # the reconstruction of the scene split by views over the same ranks
     embeds = torch.load(args.text_embeds_path, map_location="cpu") if args.text_embeds_path else None
+    if args.post_opt_eval_every < 0 or (args.post_opt_eval_every > 0 and args.post_opt_steps <= 0):
+        raise ValueError("--post_opt_eval_every K needs K >= 0 and --post_opt_steps > 0 (it evaluates the views held out of the refinement)")
+    if (args.lpips_vgg_weights is None) != (args.lpips_lin_weights is None):
+        raise ValueError("--lpips_vgg_weights and --lpips_lin_weights go together: give both or neither")
+    lpips = None
+    if args.post_opt_eval_every > 0 and args.lpips_vgg_weights is not None:
+        from vist3a_amd.evaluation.lpips import get_lpips
+        lpips = get_lpips(args.lpips_vgg_weights, args.lpips_lin_weights, device)
     encode = None if (embeds is not None or args.synthetic_text) else build_text_encoder(args, device)
     for prompt in prompts:
         if encode is not None:  # the reference's own route: WanPipeline.encode_prompt(prompt, negative_prompt), 512 tokens, zero padded
@@ -125,8 +147,10 @@ def main(args):
         (save / "prompt.txt").write_text(prompt)
         g = out.gaussians
         if args.post_opt_steps > 0:   # against the frames the reconstruction saw, at the predicted context poses and intrinsics
-            g = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps, out.depth_dict,
-                       args.post_opt_depth_lambda, args.post_opt_bilateral_grid)
+            g, stats = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps, out.depth_dict,
+                              args.post_opt_depth_lambda, args.post_opt_bilateral_grid, args.post_opt_eval_every, lpips)
+            if stats is not None:
+                (save / "post_opt_stats.json").write_text(json.dumps(stats, indent=1))
         if not args.no_video:  # orbit video through the predicted context poses (reference :144-154)
             save_interpolated_video(out.pred_context_pose["extrinsic"], out.pred_context_pose["intrinsic"], 1, args.feedforward_resolution,
                                     args.feedforward_resolution, g, str(save), stitched.stitched_3d_model.decoder)

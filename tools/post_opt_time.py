@@ -4,7 +4,10 @@ activation, render forward, loss, backward (loss + render + activation), Adam ov
 harmonics against a `copy_` of the same bytes (28 B per element: p, m, v read and written, g read; the yardstick of tools/norm_time.py).
 With --bilateral_grid the step runs as with cfg.use_bilateral_grid (21 views' grids of the default shape): the slice and the
 total-variation launches are timed as a part of their own ("bilagrid": both forwards; their backwards fall into "backward", the
-grid's Adam into "adam")."""
+grid's Adam into "adam").
+A second JSON line times the evaluation-time colour fit on one image pair of the same size (csrc/color_correct.hip, 5 rounds = 12
+launches) next to the plain MSE (ops.image_mse, 2 launches): milliseconds, and the fit's bytes read per round (img + one channel
+of ref per workgroup row, 3 x 16 B per pixel) over its time.  It runs outside the step: the loop never calls it."""
 import argparse
 import json
 import math
@@ -91,6 +94,23 @@ def main():
     print(json.dumps(dict(gaussians=U, size=W, bilateral_grid=bool(a.bilateral_grid), step_ms=round(sum(med.values()), 3), **{n + "_ms": round(x, 3) for n, x in med.items()},
                           adam_sh_elements=sh.numel(), adam_sh_ms=round(a_ms, 3), adam_sh_GBps=round(nbytes / a_ms / 1e6, 1),
                           copy_same_bytes_ms=round(c_ms, 3), copy_GBps=round(nbytes / c_ms / 1e6, 1), adam_over_copy=round(a_ms / c_ms, 2))))
+    # the evaluation-time colour fit and the plain MSE on one image pair
+    img = (target * 0.85 + 0.05).contiguous()
+    tf, tm = [], []
+    for it in range(a.warmup + a.iters):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        ops.color_correct(img, target)
+        e[1].record()
+        ops.image_mse(img, target)
+        e[2].record()
+        torch.cuda.synchronize()
+        if it >= a.warmup:
+            tf.append(e[0].elapsed_time(e[1]))
+            tm.append(e[1].elapsed_time(e[2]))
+    f_ms, m_ms = statistics.median(tf), statistics.median(tm)
+    print(json.dumps(dict(size=W, color_correct_iters=5, color_correct_ms=round(f_ms, 3), color_correct_ms_per_round=round(f_ms / 5, 3),
+                          color_correct_read_GBps=round(5 * 48 * W * H / f_ms / 1e6, 1), image_mse_ms=round(m_ms, 3))))
 
 
 if __name__ == "__main__":

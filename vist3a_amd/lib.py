@@ -266,6 +266,32 @@ class BilagridTvArgs(C.Structure):
     ]
 
 
+class ColorCorrectArgs(C.Structure):
+    _fields_ = [
+        ("img", C.c_void_p), ("ref", C.c_void_p),
+        ("out", C.c_void_p),
+        ("N", C.c_int), ("H", C.c_int), ("W", C.c_int),
+        ("num_iters", C.c_int),
+        ("ld_img", C.c_long), ("ld_ref", C.c_long), ("ld_out", C.c_long),
+        ("img_stride", C.c_long), ("ref_stride", C.c_long), ("out_stride", C.c_long),
+        ("eps", C.c_double),
+        ("sse", C.c_void_p),
+        ("status", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
+class ImageMseArgs(C.Structure):
+    _fields_ = [
+        ("a", C.c_void_p), ("b", C.c_void_p),
+        ("N", C.c_int), ("H", C.c_int), ("W", C.c_int), ("C", C.c_int),
+        ("ld_a", C.c_long), ("ld_b", C.c_long),
+        ("a_stride", C.c_long), ("b_stride", C.c_long),
+        ("mse", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
 class AdamArgs(C.Structure):
     _fields_ = [
         ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
@@ -355,13 +381,17 @@ SYMBOLS = {
     "v3a_bilagrid_tv_workspace_bytes": (C.c_long, [C.c_int] * 4),
     "v3a_bilagrid_tv_forward": (C.c_int, [C.POINTER(BilagridTvArgs), C.c_void_p]),
     "v3a_bilagrid_tv_backward": (C.c_int, [C.POINTER(BilagridTvArgs), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v3a_color_correct_workspace_bytes": (C.c_long, [C.c_int] * 4),
+    "v3a_color_correct": (C.c_int, [C.POINTER(ColorCorrectArgs), C.c_void_p]),
+    "v3a_image_mse_workspace_bytes": (C.c_long, [C.c_int] * 4),
+    "v3a_image_mse": (C.c_int, [C.POINTER(ImageMseArgs), C.c_void_p]),
     "v3a_splat_activate": (C.c_int, [C.c_void_p] * 3 + [C.c_long] + [C.c_void_p] * 3),
     "v3a_splat_activate_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),
     "v3a_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 28   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 29   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

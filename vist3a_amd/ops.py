@@ -1584,6 +1584,71 @@ def bilagrid_to_reference(t: torch.Tensor) -> torch.Tensor:
     return t.permute(0, 4, 1, 2, 3).contiguous()
 
 
+def _image_view(t: torch.Tensor, name: str, what: str, channels: Optional[int] = None):
+    """(row stride, image stride) in elements of a float32 device view [N,H,W,C] whose rows of W C elements are contiguous"""
+    if t.requires_grad:
+        raise NotImplementedError(f"{what}: no gradient ({name} requires grad; detach it - this is a metric, not a loss)")
+    if not t.is_cuda:
+        raise ValueError(f"{what}: {name} must be a device tensor (the HIP path has no CPU fallback)")
+    if t.dtype != f32 or t.dim() != 4 or (channels is not None and t.shape[-1] != channels):
+        raise ValueError(f"{what}: {name} must be float32 [N,H,W,{channels or 'C'}], got {t.dtype} {tuple(t.shape)}")
+    N, H, W, Cc = t.shape
+    if min(N, H, W, Cc) < 1:
+        raise ValueError(f"{what}: {name} is empty, shape {tuple(t.shape)}")
+    if (Cc > 1 and t.stride(3) != 1) or (W > 1 and t.stride(2) != Cc):
+        raise ValueError(f"{what}: the pixels of a row of {name} must be contiguous (strides {t.stride()}); row and image strides are free")
+    ld = t.stride(1) if H > 1 else W * Cc
+    return ld, (t.stride(0) if N > 1 else H * ld)
+
+
+def color_correct(img: torch.Tensor, ref: torch.Tensor, num_iters: int = 5, eps: float = 0.5 / 255):
+    """The reference's color_correct (lib_bilagrid.py:56-126) per image on csrc/color_correct.hip: `img` f32 [N,H,W,3] is warped
+    towards `ref` by `num_iters` rounds of a masked least-squares fit of a quadratic colour transform (10 coefficients per output
+    channel), every image on its own; fp64 after the loads, rounded once.  Views with free row / image strides are read in place.
+    -> (corrected f32 [N,H,W,3], mse f64 [N] of corrected against ref, status int32 [N,3]).  status[n][c] != 0: in some round channel
+    c of image n had fewer than 10 usable pixels (bit 0) or a singular system (bit 1) and kept the identity warp for that round
+    (the reference asserts or is undefined there).  PSNR = -10 log10(mse) is the caller's.  No gradient: an input that requires one
+    is refused."""
+    ld_i, st_i = _image_view(img, "img", "color_correct", 3)
+    ld_r, st_r = _image_view(ref, "ref", "color_correct", 3)
+    if img.shape != ref.shape:
+        raise ValueError(f"color_correct: image shapes differ: {tuple(img.shape)} vs {tuple(ref.shape)}")
+    N, H, W, _ = img.shape
+    lib = L.load()
+    need = lib.v3a_color_correct_workspace_bytes(N, H, W, int(num_iters))
+    if need < 0:
+        L.check(int(need), f"v3a_color_correct_workspace_bytes (shape {tuple(img.shape)}, num_iters {num_iters}; 1 <= num_iters <= 16 required)")
+    dev = img.device
+    ws = torch.empty((int(need) + 7) // 8, device=dev, dtype=torch.float64)
+    out = torch.empty((N, H, W, 3), device=dev, dtype=f32)
+    sse = torch.empty(N, device=dev, dtype=torch.float64)
+    status = torch.empty((N, 3), device=dev, dtype=torch.int32)
+    args = L.ColorCorrectArgs(_ptr(img), _ptr(ref), _ptr(out), N, H, W, int(num_iters), ld_i, ld_r, 3 * W, st_i, st_r, 3 * W * H,
+                              float(eps), _ptr(sse), _ptr(status), _ptr(ws), ws.numel() * 8)
+    L.check(lib.v3a_color_correct(C.byref(args), _stream()), f"v3a_color_correct (shape {tuple(img.shape)}, eps {eps})")
+    return out, sse / float(H * W * 3), status
+
+
+def image_mse(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """Per-image mean squared error of two f32 image batches [N,H,W,C] (csrc/color_correct.hip): differences and sums in fp64,
+    fixed-order reduction.  -> f64 [N] on the device; PSNR = -10 log10(mse) is the caller's.  Views with free row / image strides
+    are read in place.  No gradient: an input that requires one is refused."""
+    ld_a, st_a = _image_view(a, "a", "image_mse")
+    ld_b, st_b = _image_view(b, "b", "image_mse")
+    if a.shape != b.shape:
+        raise ValueError(f"image_mse: image shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
+    N, H, W, Cc = a.shape
+    lib = L.load()
+    need = lib.v3a_image_mse_workspace_bytes(N, H, W, Cc)
+    if need < 0:
+        L.check(int(need), f"v3a_image_mse_workspace_bytes (shape {tuple(a.shape)})")
+    ws = torch.empty((int(need) + 7) // 8, device=a.device, dtype=torch.float64)
+    mse = torch.empty(N, device=a.device, dtype=torch.float64)
+    args = L.ImageMseArgs(_ptr(a), _ptr(b), N, H, W, Cc, ld_a, ld_b, st_a, st_b, _ptr(mse), _ptr(ws), ws.numel() * 8)
+    L.check(lib.v3a_image_mse(C.byref(args), _stream()), f"v3a_image_mse (shape {tuple(a.shape)})")
+    return mse
+
+
 class _SplatActivate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, log_scales, quats, logits):

@@ -52,6 +52,7 @@ class PostOptConfig:
     bilagrid_lr: float = 2e-3        # :707, times sqrt(batch_size) = 1
     bilagrid_warmup_steps: int = 1000   # :839: LinearLR(0.01 -> 1) chained with the decay to 1 % over max_steps
     bilagrid_tv_lambda: float = 10.0    # :963
+    test_every: int = 0              # k > 0: the views with index % k == 0 are held out of the loop (the reference's dataset split, test_every)
     # ours
     params: Tuple[str, ...] = ("means", "scales", "quats", "opacities", "sh0", "shN")
     seed: int = 0
@@ -94,6 +95,27 @@ def view_order(n_views: int, steps: int, seed: int) -> list:
     while len(out) < steps:
         out += torch.randperm(n_views, generator=g).tolist()
     return out[:steps]
+
+
+def train_views(n_views: int, test_every: int) -> list:
+    """The views the loop may show: all of them, or with test_every = k > 0 those with index % k != 0 (the others are held out for
+    post_opt.evaluate_views, as the reference's parser splits its dataset)."""
+    k = int(test_every)
+    if k < 0:
+        raise ValueError(f"PostOptConfig.test_every must be >= 0, got {test_every!r}")
+    train = [i for i in range(n_views) if k == 0 or i % k != 0]
+    if not train:
+        raise ValueError(f"test_every = {k} holds out all {n_views} views: no view is left to train on (use a value >= 2 with at "
+                         "least 2 views)")
+    return train
+
+
+def train_view_order(n_views: int, steps: int, seed: int, test_every: int = 0) -> list:
+    """The view of every step of post_optimize: view_order over the training views.  With test_every = 0 it is view_order itself."""
+    if int(test_every) == 0:
+        return view_order(n_views, steps, seed)
+    train = train_views(n_views, test_every)
+    return [train[j] for j in view_order(len(train), steps, seed)]
 
 
 def _single(gaussians: Gaussians) -> None:
@@ -163,7 +185,10 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
 
     With cfg.depth_loss the step's loss is photometric + cfg.depth_lambda * ops.depth_loss(rendered depth, alpha, depths[j],
     depth_masks[j], cfg.scene_scale): `depths` f32 [V,H,W] on the device are z along the camera axis in the units of `extrinsics`,
-    `depth_masks` bool / uint8 [V,H,W] (or None: every pixel with a positive finite depth).  Without cfg.depth_loss `depths` is ignored."""
+    `depth_masks` bool / uint8 [V,H,W] (or None: every pixel with a positive finite depth).  Without cfg.depth_loss `depths` is ignored.
+
+    With cfg.test_every = k > 0 the views with index % k == 0 are never shown (train_view_order); their images and depths
+    are not read, and there is one bilateral grid per TRAINING view, in their order.  post_opt.evaluate_views scores them."""
     cfg = cfg or PostOptConfig()
     cfg.check_bilagrid()
     _single(gaussians)
@@ -191,16 +216,19 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
         raise ValueError("images must be on the device (the HIP path has no CPU fallback)")
     steps = cfg.max_steps if steps is None else int(steps)
     trained = cfg.trained()
-    splats = splats if splats is not None else create_splats(gaussians, cfg, V)
+    train = train_views(V, cfg.test_every)
+    grid_of = {j: g for g, j in enumerate(train)}     # the identity when nothing is held out
+    Vt = len(train)
+    splats = splats if splats is not None else create_splats(gaussians, cfg, Vt)
     p, m, v = splats["params"], splats["m"], splats["v"]
     bil = cfg.use_bilateral_grid
     if bil:
         if "bil_grids" not in splats:
-            add_bilateral_grids(splats, cfg, V)
+            add_bilateral_grids(splats, cfg, Vt)
         GX, GY, Lz = cfg.bilateral_grid_shape
-        if tuple(splats["bil_grids"].shape) != (V, Lz, GY, GX, 12):
-            raise ValueError(f"splats['bil_grids'] has shape {tuple(splats['bil_grids'].shape)}, the {V} views and "
-                             f"cfg.bilateral_grid_shape want {(V, Lz, GY, GX, 12)}")
+        if tuple(splats["bil_grids"].shape) != (Vt, Lz, GY, GX, 12):
+            raise ValueError(f"splats['bil_grids'] has shape {tuple(splats['bil_grids'].shape)}, the {Vt} training views and "
+                             f"cfg.bilateral_grid_shape want {(Vt, Lz, GY, GX, 12)}")
     dev = p["means"].device
     Ksh = p["sh"].shape[-1]
     sh_degree = isqrt(Ksh) - 1
@@ -215,12 +243,12 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     if bil:
         leaves.append(splats["bil_grids"].requires_grad_(True))
     try:
-        for i, j in enumerate(view_order(V, steps, cfg.seed)):
+        for i, j in enumerate(train_view_order(V, steps, cfg.seed, cfg.test_every)):
             cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
             color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
                                         sh_degree=sh_degree, sh_layout=1, background=background, clamp_rgb=True, workspace=ws)
             if bil:
-                color = ops.bilagrid_slice(color, splats["bil_grids"][j:j + 1])
+                color = ops.bilagrid_slice(color, splats["bil_grids"][grid_of[j]:grid_of[j] + 1])
             loss, l1, ssim = ops.photometric_loss(color, images[j:j + 1], cfg.ssim_lambda)
             if cfg.depth_loss:
                 dterm, _ = ops.depth_loss(depth, alpha, depths[j:j + 1], None if depth_masks is None else depth_masks[j:j + 1], cfg.scene_scale)

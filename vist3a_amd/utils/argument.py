@@ -50,6 +50,15 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
     g.add_argument("--post_opt_bilateral_grid", action="store_true",
                    help="post-optimisation with one bilateral grid per view (the reference's use_bilateral_grid): the grids absorb the "
                         "frames' exposure and white-balance drift instead of the scene; they are not exported")
+    g.add_argument("--post_opt_eval_every", type=int, default=0, metavar="K",
+                   help="hold the views with index %% K == 0 out of the post-optimisation (the reference's test_every) and evaluate them "
+                        "before and after it: PSNR, SSIM, the number of Gaussians and a time per image - with --post_opt_bilateral_grid "
+                        "also the colour-corrected cc_psnr - into post_opt_stats.json next to gaussians.ply; 0 = off")
+    g.add_argument("--lpips_vgg_weights", type=str, default=None, metavar="PATH",
+                   help="with --post_opt_eval_every: torchvision's VGG-16 state dict (vgg16-397923af.pth); with --lpips_lin_weights adds "
+                        "LPIPS to post_opt_stats.json")
+    g.add_argument("--lpips_lin_weights", type=str, default=None, metavar="PATH",
+                   help="with --post_opt_eval_every: the lpips package's weights/v0.1/vgg.pth (lin0..lin4)")
     return p
 
 
