@@ -29,9 +29,10 @@
 //
 // Total variation of [V,L,GY,GX,12]: for each of the axes L, GY, GX the sum of squared forward differences divided by
 // 12 * (L GY GX with that axis' size - 1), added in that order and divided by V.  fp64 partials per workgroup (one per axis) on a grid
-// that depends on the size only, then a one-workgroup fixed-order reduction.  Backward: one launch, every element written once,
+// that depends on the size only, then a one-workgroup reduction (fixed_sum.h).  Backward: one launch, every element written once,
 // d_out times a coefficient that does not depend on it.
 #include "common.h"
+#include "fixed_sum.h"
 #include "../../include/vist3a_hip.h"
 
 #pragma clang fp contract(off)
@@ -238,20 +239,6 @@ struct TvP {
   long n;                             // V L GY GX 12
 };
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // part[0..2][blocks]: squared forward differences along L, GY, GX
 __global__ void __launch_bounds__(THREADS) bilagrid_tv_fwd_kernel(const TvP p, double* part) {
   __shared__ double red[THREADS];
@@ -265,7 +252,7 @@ __global__ void __launch_bounds__(THREADS) bilagrid_tv_fwd_kernel(const TvP p, d
     if (y < p.GY - 1) { const double d = (double)p.grids[e + sy] - c; ay += d * d; }
     if (x < p.GX - 1) { const double d = (double)p.grids[e + sx] - c; ax += d * d; }
   }
-  const double tl = block_sum(al, red), ty = block_sum(ay, red), tx = block_sum(ax, red);
+  const double tl = block_sum<THREADS>(al, red), ty = block_sum<THREADS>(ay, red), tx = block_sum<THREADS>(ax, red);
   if (threadIdx.x == 0) {
     part[blockIdx.x] = tl;
     part[gridDim.x + blockIdx.x] = ty;
@@ -283,7 +270,7 @@ __global__ void __launch_bounds__(THREADS) bilagrid_tv_reduce_kernel(const TvP p
   for (int a = 0; a < 3; ++a) {
     double v = 0.0;
     for (int t = threadIdx.x; t < parts; t += THREADS) v += part[(long)a * parts + t];
-    s[a] = block_sum(v, red);
+    s[a] = block_sum<THREADS>(v, red);
   }
   if (threadIdx.x == 0) out[0] = (s[0] / count_l(p) + s[1] / count_y(p) + s[2] / count_x(p)) / (double)p.V;
 }
@@ -315,11 +302,6 @@ bool bad_slice(const v3a_bilagrid_slice_args* a) {
   return a->N < 1 || a->H < 1 || a->W < 1 || (double)a->N * a->H * a->W * 3.0 > 2147483647.0 || bad_grid(a->N, a->GX, a->GY, a->L);
 }
 
-int blocks_for(long n) {
-  const long need = (n + THREADS - 1) / THREADS;
-  return (int)(need < 1 ? 1 : (need > MAX_BLOCKS ? MAX_BLOCKS : need));
-}
-
 SliceP slice_params(const v3a_bilagrid_slice_args* a) {
   SliceP p;
   p.rgb = a->rgb; p.grids = a->grids;
@@ -342,7 +324,7 @@ extern "C" int v3a_bilagrid_slice_forward(const v3a_bilagrid_slice_args* a, floa
   if (!a || !a->rgb || !a->grids || !out) return V3A_ERR_ARG;
   if (bad_slice(a)) return V3A_ERR_SHAPE;
   const SliceP p = slice_params(a);
-  hipLaunchKernelGGL(bilagrid_slice_fwd_kernel, dim3(blocks_for((long)p.N * p.H * p.W)), dim3(THREADS), 0, (hipStream_t)stream, p, out);
+  hipLaunchKernelGGL(bilagrid_slice_fwd_kernel, dim3(grid_blocks((long)p.N * p.H * p.W, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, (hipStream_t)stream, p, out);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
@@ -351,7 +333,7 @@ extern "C" int v3a_bilagrid_slice_backward(const v3a_bilagrid_slice_args* a, con
   if (bad_slice(a)) return V3A_ERR_SHAPE;
   const SliceP p = slice_params(a);
   if (d_rgb) {
-    hipLaunchKernelGGL(bilagrid_slice_bwd_rgb_kernel, dim3(blocks_for((long)p.N * p.H * p.W)), dim3(THREADS), 0, (hipStream_t)stream, p, d_out, d_rgb);
+    hipLaunchKernelGGL(bilagrid_slice_bwd_rgb_kernel, dim3(grid_blocks((long)p.N * p.H * p.W, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, (hipStream_t)stream, p, d_out, d_rgb);
     if (hipGetLastError() != hipSuccess) return V3A_ERR_LAUNCH;
   }
   if (d_grids) {
@@ -364,7 +346,7 @@ extern "C" int v3a_bilagrid_slice_backward(const v3a_bilagrid_slice_args* a, con
 
 extern "C" long v3a_bilagrid_tv_workspace_bytes(int V, int GX, int GY, int L) {
   if (bad_grid(V, GX, GY, L)) return V3A_ERR_SHAPE;
-  return 3L * blocks_for((long)V * L * GY * GX * 12) * (long)sizeof(double);
+  return 3L * grid_blocks((long)V * L * GY * GX * 12, THREADS, MAX_BLOCKS) * (long)sizeof(double);
 }
 
 extern "C" int v3a_bilagrid_tv_forward(const v3a_bilagrid_tv_args* a, void* stream) {
@@ -373,7 +355,7 @@ extern "C" int v3a_bilagrid_tv_forward(const v3a_bilagrid_tv_args* a, void* stre
   if (!a->workspace || ((uintptr_t)a->workspace & 7) || a->workspace_bytes < v3a_bilagrid_tv_workspace_bytes(a->V, a->GX, a->GY, a->L))
     return V3A_ERR_WORKSPACE;
   const TvP p = tv_params(a);
-  const int blocks = blocks_for(p.n);
+  const int blocks = grid_blocks(p.n, THREADS, MAX_BLOCKS);
   double* part = (double*)a->workspace;
   hipLaunchKernelGGL(bilagrid_tv_fwd_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, p, part);
   if (hipGetLastError() != hipSuccess) return V3A_ERR_LAUNCH;
@@ -385,6 +367,6 @@ extern "C" int v3a_bilagrid_tv_backward(const v3a_bilagrid_tv_args* a, const dou
   if (!a || !a->grids || !d_out || !d_grids) return V3A_ERR_ARG;
   if (bad_grid(a->V, a->GX, a->GY, a->L)) return V3A_ERR_SHAPE;
   const TvP p = tv_params(a);
-  hipLaunchKernelGGL(bilagrid_tv_bwd_kernel, dim3(blocks_for(p.n)), dim3(THREADS), 0, (hipStream_t)stream, p, d_out, d_grids);
+  hipLaunchKernelGGL(bilagrid_tv_bwd_kernel, dim3(grid_blocks(p.n, THREADS, MAX_BLOCKS)), dim3(THREADS), 0, (hipStream_t)stream, p, d_out, d_grids);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

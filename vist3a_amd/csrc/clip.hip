@@ -16,12 +16,13 @@
 //        32 keys in LDS (read as broadcasts: every lane reads the same address), online softmax with one rescale per tile.  A row's keys are
 //        visited in index order by one lane: results do not depend on the launch's batch, head count or on other rows.
 //   4. clip_score_kernel       fp64: s_f = max(100 <i_f, t> / (|i_f| |t|), 0) for F image embeddings against one text embedding, and
-//        their mean summed in frame order.  One workgroup, fixed-order reductions, no atomics.
+//        their mean summed in frame order.  One workgroup, the reductions of fixed_sum.h, no atomics.
 //
 // Bounds: the resize passes and the token assembly are streaming passes (bytes); attention_f32 does 2 S^2 64 FMAs
 // per head, one lane per row, behind LDS broadcast reads of 16 B per 4 FMAs at one wave per SIMD - LDS / global latency, not the VALU,
 // is what most likely bounds it (not measured).
 #include "common.h"
+#include "fixed_sum.h"
 #include "../../include/vist3a_hip.h"
 
 #pragma clang fp contract(off)
@@ -273,26 +274,12 @@ __global__ void __launch_bounds__(QT) attention_f32_kernel(AttnP p) {
 }
 
 // ------------------------------------------------------------------------------------------------ score head (fp64)
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ void __launch_bounds__(THREADS) clip_score_kernel(const float* img, const float* txt, int F, int D, double* scores, double* mean) {
   __shared__ double red[THREADS];
   const int tid = threadIdx.x;
   double tt = 0.0;
   for (int c = tid; c < D; c += THREADS) tt += (double)txt[c] * (double)txt[c];
-  tt = block_sum(tt, red);
+  tt = block_sum<THREADS>(tt, red);
   double total = 0.0;
   for (int f = 0; f < F; ++f) {
     double ii = 0.0, it = 0.0;
@@ -301,8 +288,8 @@ __global__ void __launch_bounds__(THREADS) clip_score_kernel(const float* img, c
       ii += a * a;
       it += a * (double)txt[c];
     }
-    ii = block_sum(ii, red);
-    it = block_sum(it, red);
+    ii = block_sum<THREADS>(ii, red);
+    it = block_sum<THREADS>(it, red);
     double s = 100.0 * (it / (sqrt(ii) * sqrt(tt)));
     s = s < 0.0 ? 0.0 : s;   // torchmetrics: max(score, 0); a NaN (zero embedding) stays NaN, as there
     if (tid == 0) scores[f] = s;

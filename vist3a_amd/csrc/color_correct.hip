@@ -25,7 +25,7 @@
 //              channel's warp of this round is the identity (x[c] passes through, still clipped).  The flags of all rounds are
 //              OR-ed into status[n][c].
 //  apply       grid (B, N): x through all K warps, out = (float)x, and the squared difference of the STORED value to ref in fp64,
-//              per workgroup, fixed order.
+//              per workgroup (fixed_sum.h).
 //  finish      grid (N): the B partials in block order -> sse[n]; status.
 // B depends on H W alone (never on N), so an image's result does not depend on its neighbours in the call; no atomics anywhere:
 // bit-identical run to run.
@@ -35,6 +35,7 @@
 // Layout: [N,H,W,3] with the pixel's channels contiguous; row stride ld_* and image stride *_stride in elements, so a crop or a
 // slice of a larger buffer is read and written in place.  Only the [H, 3 W] region of each image is touched.
 #include "common.h"
+#include "fixed_sum.h"
 #include "../../include/vist3a_hip.h"
 
 #pragma clang fp contract(off)
@@ -185,20 +186,6 @@ __global__ void __launch_bounds__(SOLVE_THREADS) cc_solve_kernel(const CcP p, in
   if (t == 0) p.flags[((long)n * p.K + it) * 3 + c] = fail;
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ void __launch_bounds__(THREADS) cc_apply_kernel(const CcP p) {
   __shared__ double wl[MAX_ITERS * 3 * NF];
   __shared__ double red[THREADS];
@@ -221,7 +208,7 @@ __global__ void __launch_bounds__(THREADS) cc_apply_kernel(const CcP p) {
       err += d * d;
     }
   }
-  const double total = block_sum(err, red);
+  const double total = block_sum<THREADS>(err, red);
   if (t == 0) p.part_sse[(long)n * gridDim.x + blockIdx.x] = total;
 }
 
@@ -255,7 +242,7 @@ __global__ void __launch_bounds__(THREADS) mse_partial_kernel(const MseP p, doub
     const double d = (double)p.a[(long)n * p.a_stride + i * p.ld_a + j] - (double)p.b[(long)n * p.b_stride + i * p.ld_b + j];
     err += d * d;
   }
-  const double s = block_sum(err, red);
+  const double s = block_sum<THREADS>(err, red);
   if (t == 0) part[(long)n * gridDim.x + blockIdx.x] = s;
 }
 
@@ -266,11 +253,6 @@ __global__ void __launch_bounds__(64) mse_finish_kernel(const double* part, int 
     for (int b = 0; b < blocks; ++b) s += part[(long)n * blocks + b];
     mse[n] = s / count;
   }
-}
-
-int blocks_for(long n) {
-  const long need = (n + THREADS - 1) / THREADS;
-  return (int)(need < 1 ? 1 : (need > MAX_BLOCKS ? MAX_BLOCKS : need));
 }
 
 bool bad_image(int N, int H, int W, int C) {
@@ -285,7 +267,7 @@ bool bad_strides(long ld, long image, int N, int H, long cols) {
 bool misaligned(const void* ptr, unsigned a) { return ((uintptr_t)ptr & (a - 1)) != 0; }
 
 long cc_bytes(int N, int H, int W, int K, long* off_warps, long* off_sse, long* off_flags) {
-  const long B = blocks_for((long)H * W);
+  const long B = grid_blocks((long)H * W, THREADS, MAX_BLOCKS);
   const long part = (long)N * 3 * B * NS, warps = (long)N * K * 3 * NF, sse = (long)N * B, flags = (long)N * K * 3;
   if (off_warps) *off_warps = part;
   if (off_sse) *off_sse = part + warps;
@@ -325,7 +307,7 @@ extern "C" int v3a_color_correct(const v3a_color_correct_args* a, void* stream) 
   p.warps = ws + off_warps;
   p.part_sse = ws + off_sse;
   p.flags = (int*)(ws + off_flags);
-  const int B = blocks_for((long)p.H * p.W);
+  const int B = grid_blocks((long)p.H * p.W, THREADS, MAX_BLOCKS);
   hipStream_t st = (hipStream_t)stream;
   for (int it = 0; it < p.K; ++it) {
     hipLaunchKernelGGL(cc_accumulate_kernel, dim3(B, 3, p.N), dim3(THREADS), 0, st, p, it);
@@ -341,7 +323,7 @@ extern "C" int v3a_color_correct(const v3a_color_correct_args* a, void* stream) 
 
 extern "C" long v3a_image_mse_workspace_bytes(int N, int H, int W, int C) {
   if (bad_image(N, H, W, C)) return V3A_ERR_SHAPE;
-  return (long)N * blocks_for((long)H * W * C) * (long)sizeof(double);
+  return (long)N * grid_blocks((long)H * W * C, THREADS, MAX_BLOCKS) * (long)sizeof(double);
 }
 
 extern "C" int v3a_image_mse(const v3a_image_mse_args* a, void* stream) {
@@ -356,7 +338,7 @@ extern "C" int v3a_image_mse(const v3a_image_mse_args* a, void* stream) {
   p.a = a->a; p.b = a->b;
   p.ld_a = a->ld_a; p.ld_b = a->ld_b; p.a_stride = a->a_stride; p.b_stride = a->b_stride;
   p.N = a->N; p.H = a->H; p.W = a->W; p.C = a->C;
-  const int B = blocks_for((long)p.H * p.W * p.C);
+  const int B = grid_blocks((long)p.H * p.W * p.C, THREADS, MAX_BLOCKS);
   double* part = (double*)a->workspace;
   hipLaunchKernelGGL(mse_partial_kernel, dim3(B, p.N), dim3(THREADS), 0, (hipStream_t)stream, p, part);
   if (hipGetLastError() != hipSuccess) return V3A_ERR_LAUNCH;

@@ -17,7 +17,7 @@
 //
 // Forward: one grid-stride pass, 16-byte loads of depth / alpha / depth_gt and a 4-byte load of the mask where all four pointers
 // allow, a scalar tail (and everything scalar where they do not); one fp64 partial sum and one count per workgroup, then a
-// one-workgroup reduction in a fixed order.  The grid depends on the size only: bit-identical run to run, no atomics.
+// one-workgroup reduction in the order of fixed_sum.h.  The grid depends on the size only: bit-identical run to run, no atomics.
 // Backward: one launch, every element of d_depth and d_alpha written exactly once (zero where the pixel is unused or E <= 0), M read
 // from the forward's output on the device.  With s = sign(disp - 1 / depth_gt), sign(0) = 0:
 //   dL/dE = -s scale / (M E^2),   d_depth = d_out dL/dE / a_c,   d_alpha = alpha > 1e-10 ? -d_out dL/dE depth / alpha^2 : 0
@@ -26,6 +26,7 @@
 // with H W % 4 != 0, for instance) every pixel of the call takes the scalar loop, on the same grid; the results are the same.
 // HBM-bound: 13 bytes read per pixel forward, 13 read and 8 written backward.
 #include "common.h"
+#include "fixed_sum.h"
 #include "../../include/vist3a_hip.h"
 
 #pragma clang fp contract(off)
@@ -59,21 +60,6 @@ __device__ __forceinline__ void fwd_one(float depth, float alpha, float gt, unsi
   cnt += 1;
 }
 
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const T r = red[0];
-  __syncthreads();
-  return r;
-}
-
 __global__ void __launch_bounds__(THREADS) depth_loss_fwd_kernel(const DepthP p, double* part_sum, long long* part_cnt) {
   __shared__ double red_s[THREADS];
   __shared__ long long red_c[THREADS];
@@ -91,8 +77,8 @@ __global__ void __launch_bounds__(THREADS) depth_loss_fwd_kernel(const DepthP p,
   }
   for (long e = p.nvec * 4 + t0; e < p.n; e += stride)
     fwd_one(p.depth[e], p.alpha[e], p.gt[e], p.mask ? (unsigned)p.mask[e] : 1u, sum, cnt);
-  const double ts = block_sum(sum, red_s);
-  const long long tc = block_sum(cnt, red_c);
+  const double ts = block_sum<THREADS>(sum, red_s);
+  const long long tc = block_sum<THREADS>(cnt, red_c);
   if (threadIdx.x == 0) {
     part_sum[blockIdx.x] = ts;
     part_cnt[blockIdx.x] = tc;
@@ -110,8 +96,8 @@ __global__ void __launch_bounds__(THREADS) depth_loss_reduce_kernel(const double
     s += part_sum[t];
     c += part_cnt[t];
   }
-  const double ts = block_sum(s, red_s);
-  const long long tc = block_sum(c, red_c);
+  const double ts = block_sum<THREADS>(s, red_s);
+  const long long tc = block_sum<THREADS>(c, red_c);
   if (threadIdx.x == 0) {
     out[0] = tc > 0 ? scale * ts / (double)tc : 0.0;
     out[1] = (double)tc;
@@ -162,10 +148,7 @@ bool bad_shape(int C, int H, int W) {
   return C < 1 || H < 1 || W < 1 || (long)C * H * W > 0x7fffffffL;
 }
 
-int blocks_for(long n) {
-  const long need = (n / 4 + n % 4 + THREADS - 1) / THREADS;   // one thread per 16-byte group and per tail pixel
-  return (int)(need < 1 ? 1 : (need > MAX_BLOCKS ? MAX_BLOCKS : need));
-}
+long groups(long n) { return n / 4 + n % 4; }   // one thread per 16-byte group and per tail pixel
 
 // the grid of a call: from the size alone, also where the scalar path runs, so that workspace and summation order are fixed
 DepthP params(const v3a_depth_loss_args* a, const void* o1, const void* o2) {
@@ -182,7 +165,7 @@ DepthP params(const v3a_depth_loss_args* a, const void* o1, const void* o2) {
 
 extern "C" long v3a_depth_loss_workspace_bytes(int C, int H, int W) {
   if (bad_shape(C, H, W)) return V3A_ERR_SHAPE;
-  return (long)blocks_for((long)C * H * W) * (long)(sizeof(double) + sizeof(long long));
+  return (long)grid_blocks(groups((long)C * H * W), THREADS, MAX_BLOCKS) * (long)(sizeof(double) + sizeof(long long));
 }
 
 extern "C" int v3a_depth_loss_forward(const v3a_depth_loss_args* a, void* stream) {
@@ -191,7 +174,7 @@ extern "C" int v3a_depth_loss_forward(const v3a_depth_loss_args* a, void* stream
   if (!a->workspace || ((uintptr_t)a->workspace & 7) || a->workspace_bytes < v3a_depth_loss_workspace_bytes(a->C, a->H, a->W))
     return V3A_ERR_WORKSPACE;
   const DepthP p = params(a, nullptr, nullptr);
-  const int blocks = blocks_for(p.n);
+  const int blocks = grid_blocks(groups(p.n), THREADS, MAX_BLOCKS);
   double* part_sum = (double*)a->workspace;
   long long* part_cnt = (long long*)(part_sum + blocks);
   hipLaunchKernelGGL(depth_loss_fwd_kernel, dim3(blocks), dim3(THREADS), 0, (hipStream_t)stream, p, part_sum, part_cnt);
@@ -204,6 +187,6 @@ extern "C" int v3a_depth_loss_backward(const v3a_depth_loss_args* a, const doubl
   if (!a || !a->depth || !a->alpha || !a->depth_gt || !a->out || !d_out || !d_depth || !d_alpha) return V3A_ERR_ARG;
   if (bad_shape(a->C, a->H, a->W)) return V3A_ERR_SHAPE;
   const DepthP p = params(a, d_depth, d_alpha);
-  hipLaunchKernelGGL(depth_loss_bwd_kernel, dim3(blocks_for(p.n)), dim3(THREADS), 0, (hipStream_t)stream, p, a->out, d_out, d_depth, d_alpha);
+  hipLaunchKernelGGL(depth_loss_bwd_kernel, dim3(grid_blocks(groups(p.n), THREADS, MAX_BLOCKS)), dim3(THREADS), 0, (hipStream_t)stream, p, a->out, d_out, d_depth, d_alpha);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

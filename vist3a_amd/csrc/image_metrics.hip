@@ -18,10 +18,11 @@
 // Shape: one workgroup = one 32x32 tile of kept outputs of one channel of one pair.  It stages the tile + 5-pixel halo of both
 // images in LDS (dword loads of the interleaved NHWC rows), converts its channel to fp32 planes, runs the horizontal pass
 // (scipy's order: the vertical pass first, 5 moments, into LDS), then the horizontal pass and S in registers, and writes one fp64 partial sum of S and one of the
-// squared error.  A second launch reduces each pair's partials in a fixed order: no float atomics, bit-identical run to run.
+// squared error.  A second launch reduces each pair's partials in the order of fixed_sum.h: no float atomics, bit-identical run to run.
 // MSE ownership: the tile rows / columns next to an image edge also own the 5-pixel border, so every pixel of every channel is
 // counted exactly once (halo pixels are counted by the tile that owns them).
 #include "common.h"
+#include "fixed_sum.h"
 #include "../../include/vist3a_hip.h"
 
 // No contraction in this file: with fused multiply-adds, 2 ux uy + C1 and ux^2 + uy^2 + C1 (and the variance pair) could round
@@ -50,20 +51,6 @@ struct MetricsP {
   double* part_e;     // [N][C][tiles]
   int H, W, C, tiles_x, tiles;
 };
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 
 __global__ void __launch_bounds__(THREADS) ssim_tile_kernel(MetricsP p, Taps tp) {
   __shared__ unsigned int raw[2][RD][RAW_PITCH];
@@ -173,8 +160,8 @@ __global__ void __launch_bounds__(THREADS) ssim_tile_kernel(MetricsP p, Taps tp)
     }
   }
 
-  const double ts = block_sum(ssum, red);
-  const double te = block_sum(err, red);
+  const double ts = block_sum<THREADS>(ssum, red);
+  const double te = block_sum<THREADS>(err, red);
   if (tid == 0) {
     const size_t o = ((size_t)n * C + c) * p.tiles + tile;
     p.part_s[o] = ts;
@@ -194,8 +181,8 @@ __global__ void __launch_bounds__(THREADS) metrics_reduce_kernel(const double* p
       ps += part_s[o + t];
       pe += part_e[o + t];
     }
-    s_acc += block_sum(ps, red) * inv_count;     // this channel's mean S over the crop
-    e_acc += block_sum(pe, red);
+    s_acc += block_sum<THREADS>(ps, red) * inv_count;     // this channel's mean S over the crop
+    e_acc += block_sum<THREADS>(pe, red);
   }
   if (tid == 0) {
     ssim[n] = s_acc / C;

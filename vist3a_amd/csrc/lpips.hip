@@ -11,7 +11,7 @@
 //                           verbatim - exact, hi + lo of the output is the fp32 max of the window.
 //   3. lpips_head_kernel    per pixel of one tapped layer: f = hi + lo (exact in fp32), f^ = f / (sqrt(sum_c f^2) + 1e-10),
 //                           d = sum_c w[c] (f^0 - f^1)^2 (lpips normalize_tensor, NetLinLayer), all of it in fp64; one fp64 partial
-//                           sum of d per workgroup.  lpips_reduce_kernel sums each pair's partials in a fixed order and writes
+//                           sum of d per workgroup.  lpips_reduce_kernel sums each pair's partials in the order of fixed_sum.h and writes
 //                           the spatial mean (spatial_average), optionally added to what `out` holds (the sum over the five layers).
 //
 // Determinism: no atomics.  The head's tiling depends on (h, w, C) only - one workgroup row per pair, a fixed number of pixels per
@@ -22,6 +22,7 @@
 // Bounds (LPIPS section): all three kernels are single streaming passes, HBM-bound - every element is read once and
 // written once (input, pool) or read once (head), with 16-byte accesses.
 #include "common.h"
+#include "fixed_sum.h"
 #include "../../include/vist3a_hip.h"
 
 // No contraction: 2 x - 1 and (x - shift) / scale are separate torch ops, each rounded to fp32.
@@ -143,20 +144,6 @@ __device__ __forceinline__ double group_sum(double v) {
   return v;
 }
 
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
-
 // G = C / 8 lanes per pixel, each holding 8 channels of pred and gt in registers; THREADS / G pixels per step
 template <int G>
 __global__ void __launch_bounds__(THREADS) lpips_head_kernel(HeadP p) {
@@ -209,7 +196,7 @@ __global__ void __launch_bounds__(THREADS) lpips_head_kernel(HeadP p) {
     d = group_sum<G>(d);
     if (ok && g == 0) acc += d;
   }
-  const double s = block_sum(acc, red);
+  const double s = block_sum<THREADS>(acc, red);
   if (tid == 0) p.part[(size_t)n * p.tiles + tile] = s;
 }
 
@@ -218,7 +205,7 @@ __global__ void __launch_bounds__(THREADS) lpips_reduce_kernel(const double* par
   const int n = blockIdx.x, tid = threadIdx.x;
   double s = 0.0;
   for (int t = tid; t < tiles; t += THREADS) s += part[(size_t)n * tiles + t];
-  s = block_sum(s, red);
+  s = block_sum<THREADS>(s, red);
   if (tid == 0) {
     const double m = s * inv_hw;
     out[n] = accumulate ? out[n] + m : m;

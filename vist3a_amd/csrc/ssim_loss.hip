@@ -16,12 +16,13 @@
 // one channel of one image; it stages the tile + 10 rows / columns of both images in LDS, runs the vertical pass of the five
 // moments into LDS, then the horizontal pass, S and its derivatives in registers, and writes one fp64 partial of S, one of |x - y|
 // (tiles next to an image edge own the border pixels, as in image_metrics.hip) and, when the caller asks for a gradient, the three
-// planes dS/dmu1 (total), dS/dE[x^2], dS/dE[xy] of its positions.  A second launch (one workgroup) adds the partials in a fixed
-// order and writes loss, l1, ssim.  Backward, gather form: one workgroup = one 16 x 32 tile of INPUT pixels; pixel p sums over the
+// planes dS/dmu1 (total), dS/dE[x^2], dS/dE[xy] of its positions.  A second launch (one workgroup) adds the partials in the order of
+// fixed_sum.h and writes loss, l1, ssim.  Backward, gather form: one workgroup = one 16 x 32 tile of INPUT pixels; pixel p sums over the
 // at most 11 x 11 map positions q whose window covers it  w(p - q) (dmu1(q) + 2 x(p) dxx(q) + y(p) dxy(q)),  separably (vertical
 // pass of the three planes into LDS, horizontal pass in registers), adds the L1 term and writes d_pred once.  No atomics anywhere:
 // bit-identical run to run, and exactly linear in the incoming gradient.
 #include "common.h"
+#include "fixed_sum.h"
 #include "../../include/vist3a_hip.h"
 
 // No contraction in this file: identical images must give 2 mu1 mu2 + C1 == mu1^2 + mu2^2 + C1 (and the variance pair) bit for
@@ -50,20 +51,6 @@ struct LossP {
   double* planes;      // [3][N][C][Hm][Wm] or null
   int N, H, W, C, Hm, Wm, tiles_x, tiles_y;
 };
-
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  const int t = threadIdx.x;
-  red[t] = v;
-  __syncthreads();
-#pragma unroll
-  for (int s = THREADS / 2; s > 0; s >>= 1) {
-    if (t < s) red[t] += red[t + s];
-    __syncthreads();
-  }
-  const double r = red[0];
-  __syncthreads();
-  return r;
-}
 
 __global__ void __launch_bounds__(THREADS) ssim_loss_fwd_kernel(LossP p) {
   __shared__ float pl[2][RH][PITCH];
@@ -147,8 +134,8 @@ __global__ void __launch_bounds__(THREADS) ssim_loss_fwd_kernel(LossP p) {
     }
   }
 
-  const double ts = block_sum(ssum, red);
-  const double tl = block_sum(l1, red);
+  const double ts = block_sum<THREADS>(ssum, red);
+  const double tl = block_sum<THREADS>(l1, red);
   if (tid == 0) {
     const size_t o = ((size_t)n * C + c) * (p.tiles_x * p.tiles_y) + tile;
     p.part_s[o] = ts;
@@ -166,7 +153,7 @@ __global__ void __launch_bounds__(THREADS) ssim_loss_reduce_kernel(const double*
     ps += part_s[t];
     pl += part_l[t];
   }
-  const double s = block_sum(ps, red), l = block_sum(pl, red);
+  const double s = block_sum<THREADS>(ps, red), l = block_sum<THREADS>(pl, red);
   if (tid == 0) {
     const double ssim = s / count, l1 = l / numel;   // divisions: a sum of `count` ones gives exactly 1
     out[0] = (1.0 - lambda) * l1 + lambda * (1.0 - ssim);

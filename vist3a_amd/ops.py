@@ -25,6 +25,17 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _workspace(need: int, what: str, device):
+    """The per-call workspace of a loss / metric entry point from the answer of its *_workspace_bytes query: a negative answer is the
+    query's error code and raises as `what`.  -> (float64 tensor, its size in bytes): 8-byte aligned by its dtype, never empty, the
+    size rounded up to a multiple of 8.  Not cached: the buffer lives as long as the call's tensors do."""
+    need = int(need)
+    if need < 0:
+        L.check(need, what)
+    ws = torch.empty(max((need + 7) // 8, 1), device=device, dtype=torch.float64)
+    return ws, ws.numel() * 8
+
+
 def _chk2d(t: torch.Tensor, name: str, dtypes) -> None:
     if not t.is_cuda:
         raise ValueError(f"{name} must be a device tensor (the HIP path has no CPU fallback)")
@@ -1193,13 +1204,11 @@ def image_metrics(a_u8: torch.Tensor, b_u8: torch.Tensor):
         raise ValueError(f"image shapes differ: {tuple(a_u8.shape)} vs {tuple(b_u8.shape)}")
     N, H, W, Cc = a_u8.shape
     lib = L.load()
-    need = lib.v3a_image_metrics_workspace_bytes(N, H, W, Cc)
-    if need < 0:
-        L.check(int(need), f"v3a_image_metrics_workspace_bytes (shape {tuple(a_u8.shape)})")
-    ws = torch.empty(max(int(need), 1), device=a_u8.device, dtype=torch.uint8)
+    ws, ws_bytes = _workspace(lib.v3a_image_metrics_workspace_bytes(N, H, W, Cc),
+                              f"v3a_image_metrics_workspace_bytes (shape {tuple(a_u8.shape)})", a_u8.device)
     ssim = torch.empty(N, device=a_u8.device, dtype=torch.float64)
     mse = torch.empty(N, device=a_u8.device, dtype=torch.float64)
-    args = L.ImageMetricsArgs(_ptr(a_u8), _ptr(b_u8), N, H, W, Cc, _ptr(ssim), _ptr(mse), _ptr(ws), ws.numel())
+    args = L.ImageMetricsArgs(_ptr(a_u8), _ptr(b_u8), N, H, W, Cc, _ptr(ssim), _ptr(mse), _ptr(ws), ws_bytes)
     L.check(lib.v3a_image_metrics(C.byref(args), _stream()), "v3a_image_metrics")
     return ssim, mse
 
@@ -1247,11 +1256,9 @@ def lpips_head(x: torch.Tensor, weight: torch.Tensor, out: torch.Tensor, accumul
     if out.dtype != torch.float64 or not out.is_contiguous() or out.numel() != N or out.device != x.device:
         raise ValueError(f"out must be a contiguous f64 [{N}] tensor on {x.device}")
     lib = L.load()
-    need = lib.v3a_lpips_head_workspace_bytes(N, h, w, Cc)
-    if need < 0:
-        L.check(int(need), f"v3a_lpips_head_workspace_bytes (shape {tuple(x.shape)})")
-    ws = torch.empty(max(int(need), 1), device=x.device, dtype=torch.uint8)
-    L.check(lib.v3a_lpips_head(_ptr(x[0]), _ptr(x[1]), _ptr(weight), N, h, w, Cc, _ptr(out), int(accumulate), _ptr(ws), ws.numel(),
+    ws, ws_bytes = _workspace(lib.v3a_lpips_head_workspace_bytes(N, h, w, Cc), f"v3a_lpips_head_workspace_bytes (shape {tuple(x.shape)})",
+                              x.device)
+    L.check(lib.v3a_lpips_head(_ptr(x[0]), _ptr(x[1]), _ptr(weight), N, h, w, Cc, _ptr(out), int(accumulate), _ptr(ws), ws_bytes,
                                _stream()), "v3a_lpips_head")
     return out
 
@@ -1294,14 +1301,11 @@ def clip_preprocess(frames: torch.Tensor, tables: dict, lut: torch.Tensor, image
     u8 = torch.empty((N, S, S, 3), device=frames.device, dtype=torch.uint8) if want_u8 else None
     pix = torch.empty((N, 3, S, S), device=frames.device, dtype=f32) if want_f32 else None
     lib = L.load()
-    need = lib.v3a_clip_preprocess_workspace_bytes(N, rows, S)
-    if need < 0:
-        L.check(int(need), "v3a_clip_preprocess_workspace_bytes")
-    ws = torch.empty(int(need), device=frames.device, dtype=torch.uint8)
+    ws, ws_bytes = _workspace(lib.v3a_clip_preprocess_workspace_bytes(N, rows, S), "v3a_clip_preprocess_workspace_bytes", frames.device)
     args = L.ClipPreprocessArgs(_ptr(frames), _ptr(tables["x_bounds"]), _ptr(tables["x_coeffs"]), _ptr(tables["y_bounds"]),
                                 _ptr(tables["y_coeffs"]), _ptr(lut), _ptr(patches[0]), _ptr(patches[1]), _ptr(u8), _ptr(pix),
                                 N, H, W, S, P, ldk, tables["x_coeffs"].shape[1], tables["y_coeffs"].shape[1], row0, rows,
-                                _ptr(ws), ws.numel())
+                                _ptr(ws), ws_bytes)
     L.check(lib.v3a_clip_preprocess(C.byref(args), _stream()), "v3a_clip_preprocess")
     return patches, u8, pix
 
@@ -1381,16 +1385,14 @@ class _PhotometricLoss(torch.autograd.Function):
     def forward(ctx, pred, target, ssim_lambda):
         N, H, W, Cc = pred.shape
         lib = L.load()
-        need = lib.v3a_photometric_loss_workspace_bytes(N, H, W, Cc)
-        if need < 0:
-            L.check(int(need), f"v3a_photometric_loss_workspace_bytes (shape {tuple(pred.shape)}; H, W >= 11 and C <= 4 required)")
         dev = pred.device
-        ws = torch.empty(int(need), device=dev, dtype=torch.uint8)
+        ws, ws_bytes = _workspace(lib.v3a_photometric_loss_workspace_bytes(N, H, W, Cc),
+                                  f"v3a_photometric_loss_workspace_bytes (shape {tuple(pred.shape)}; H, W >= 11 and C <= 4 required)", dev)
         planes = None
         if ctx.needs_input_grad[0]:
             planes = torch.empty(int(lib.v3a_photometric_loss_planes_bytes(N, H, W, Cc)) // 8, device=dev, dtype=torch.float64)
         out = torch.empty(3, device=dev, dtype=torch.float64)
-        args = L.PhotometricLossArgs(_ptr(pred), _ptr(target), N, H, W, Cc, float(ssim_lambda), _ptr(out), _ptr(ws), ws.numel(),
+        args = L.PhotometricLossArgs(_ptr(pred), _ptr(target), N, H, W, Cc, float(ssim_lambda), _ptr(out), _ptr(ws), ws_bytes,
                                      _ptr(planes), planes.numel() * 8 if planes is not None else 0)
         L.check(lib.v3a_photometric_loss_forward(C.byref(args), _stream()), "v3a_photometric_loss_forward")
         if planes is not None:
@@ -1430,13 +1432,10 @@ class _DepthLoss(torch.autograd.Function):
     def forward(ctx, depth, alpha, depth_gt, mask, scale):
         Cc, H, W = depth.shape
         lib = L.load()
-        need = lib.v3a_depth_loss_workspace_bytes(Cc, H, W)
-        if need < 0:
-            L.check(int(need), f"v3a_depth_loss_workspace_bytes (shape {tuple(depth.shape)})")
         dev = depth.device
-        ws = torch.empty((int(need) + 7) // 8, device=dev, dtype=torch.float64)
+        ws, ws_bytes = _workspace(lib.v3a_depth_loss_workspace_bytes(Cc, H, W), f"v3a_depth_loss_workspace_bytes (shape {tuple(depth.shape)})", dev)
         out = torch.empty(2, device=dev, dtype=torch.float64)
-        args = L.DepthLossArgs(_ptr(depth), _ptr(alpha), _ptr(depth_gt), _ptr(mask), Cc, H, W, float(scale), _ptr(out), _ptr(ws), ws.numel() * 8)
+        args = L.DepthLossArgs(_ptr(depth), _ptr(alpha), _ptr(depth_gt), _ptr(mask), Cc, H, W, float(scale), _ptr(out), _ptr(ws), ws_bytes)
         L.check(lib.v3a_depth_loss_forward(C.byref(args), _stream()), "v3a_depth_loss_forward")
         ctx.save_for_backward(depth, alpha, depth_gt, mask, out)
         ctx.scale = float(scale)
@@ -1532,12 +1531,10 @@ class _BilagridTv(torch.autograd.Function):
     def forward(ctx, grids):
         V, Lz, GY, GX, _ = grids.shape
         lib = L.load()
-        need = lib.v3a_bilagrid_tv_workspace_bytes(V, GX, GY, Lz)
-        if need < 0:
-            L.check(int(need), f"v3a_bilagrid_tv_workspace_bytes (grids {tuple(grids.shape)})")
-        ws = torch.empty((int(need) + 7) // 8, device=grids.device, dtype=torch.float64)
+        ws, ws_bytes = _workspace(lib.v3a_bilagrid_tv_workspace_bytes(V, GX, GY, Lz),
+                                  f"v3a_bilagrid_tv_workspace_bytes (grids {tuple(grids.shape)})", grids.device)
         out = torch.empty(1, device=grids.device, dtype=torch.float64)
-        args = L.BilagridTvArgs(_ptr(grids), V, GX, GY, Lz, _ptr(out), _ptr(ws), ws.numel() * 8)
+        args = L.BilagridTvArgs(_ptr(grids), V, GX, GY, Lz, _ptr(out), _ptr(ws), ws_bytes)
         L.check(lib.v3a_bilagrid_tv_forward(C.byref(args), _stream()), "v3a_bilagrid_tv_forward")
         ctx.save_for_backward(grids)
         return out[0]
@@ -1615,16 +1612,14 @@ def color_correct(img: torch.Tensor, ref: torch.Tensor, num_iters: int = 5, eps:
         raise ValueError(f"color_correct: image shapes differ: {tuple(img.shape)} vs {tuple(ref.shape)}")
     N, H, W, _ = img.shape
     lib = L.load()
-    need = lib.v3a_color_correct_workspace_bytes(N, H, W, int(num_iters))
-    if need < 0:
-        L.check(int(need), f"v3a_color_correct_workspace_bytes (shape {tuple(img.shape)}, num_iters {num_iters}; 1 <= num_iters <= 16 required)")
     dev = img.device
-    ws = torch.empty((int(need) + 7) // 8, device=dev, dtype=torch.float64)
+    ws, ws_bytes = _workspace(lib.v3a_color_correct_workspace_bytes(N, H, W, int(num_iters)),
+                              f"v3a_color_correct_workspace_bytes (shape {tuple(img.shape)}, num_iters {num_iters}; 1 <= num_iters <= 16 required)", dev)
     out = torch.empty((N, H, W, 3), device=dev, dtype=f32)
     sse = torch.empty(N, device=dev, dtype=torch.float64)
     status = torch.empty((N, 3), device=dev, dtype=torch.int32)
     args = L.ColorCorrectArgs(_ptr(img), _ptr(ref), _ptr(out), N, H, W, int(num_iters), ld_i, ld_r, 3 * W, st_i, st_r, 3 * W * H,
-                              float(eps), _ptr(sse), _ptr(status), _ptr(ws), ws.numel() * 8)
+                              float(eps), _ptr(sse), _ptr(status), _ptr(ws), ws_bytes)
     L.check(lib.v3a_color_correct(C.byref(args), _stream()), f"v3a_color_correct (shape {tuple(img.shape)}, eps {eps})")
     return out, sse / float(H * W * 3), status
 
@@ -1639,12 +1634,9 @@ def image_mse(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
         raise ValueError(f"image_mse: image shapes differ: {tuple(a.shape)} vs {tuple(b.shape)}")
     N, H, W, Cc = a.shape
     lib = L.load()
-    need = lib.v3a_image_mse_workspace_bytes(N, H, W, Cc)
-    if need < 0:
-        L.check(int(need), f"v3a_image_mse_workspace_bytes (shape {tuple(a.shape)})")
-    ws = torch.empty((int(need) + 7) // 8, device=a.device, dtype=torch.float64)
+    ws, ws_bytes = _workspace(lib.v3a_image_mse_workspace_bytes(N, H, W, Cc), f"v3a_image_mse_workspace_bytes (shape {tuple(a.shape)})", a.device)
     mse = torch.empty(N, device=a.device, dtype=torch.float64)
-    args = L.ImageMseArgs(_ptr(a), _ptr(b), N, H, W, Cc, ld_a, ld_b, st_a, st_b, _ptr(mse), _ptr(ws), ws.numel() * 8)
+    args = L.ImageMseArgs(_ptr(a), _ptr(b), N, H, W, Cc, ld_a, ld_b, st_a, st_b, _ptr(mse), _ptr(ws), ws_bytes)
     L.check(lib.v3a_image_mse(C.byref(args), _stream()), f"v3a_image_mse (shape {tuple(a.shape)})")
     return mse
 
