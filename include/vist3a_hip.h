@@ -38,7 +38,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 29) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 30) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -470,6 +470,10 @@ typedef struct {
   float* depths;         /* out [C,U] camera z */
   float* conics;         /* out [C,U,3] inverse 2D covariance (a,b,c) */
   float* colors;         /* out [C,U,4] rgb + depth */
+  int rasterize_mode;    /* 0: classic; 1: antialiased (gsplat rasterize_mode="antialiased", the Mip-Splatting 2D filter); other: -1 */
+  float* compensations;  /* out [C,U], mode 1 only (required there: NULL returns -1; ignored in mode 0):
+                            sqrt(max(0, det(J Cc J^T) / det(J Cc J^T + eps2d I))), 0 for a culled entry.  Culling, radii, conics,
+                            means2d and colours are those of mode 0, bit for bit: gsplat culls and sizes on the blurred covariance. */
 } v3a_gs_project_args;
 int v3a_gs_project(const v3a_gs_project_args* a, void* stream);
 
@@ -491,6 +495,7 @@ typedef struct {
   long* n_isect;            /* HOST pointer: intersections found */
   unsigned int* tile_offsets_out;  /* optional [C*ntiles+1] */
   unsigned int* flatten_ids_out;   /* optional [max_isect]: entry ids c*U+g in composite order */
+  const float* compensations;      /* [C,U] of v3a_gs_project (mode 1) or NULL: entry c*U+g draws with opacities[g] * compensations[c*U+g] */
 } v3a_gs_rasterize_args;
 long v3a_gs_rasterize_workspace_bytes(long U, int C, int width, int height, long max_isect);
 int v3a_gs_rasterize(const v3a_gs_rasterize_args* a, void* stream);
@@ -499,7 +504,11 @@ int v3a_gs_rasterize(const v3a_gs_rasterize_args* a, void* stream);
  * spherical_harmonics_bwd hand torch.autograd for the call above.  fp32; no float atomics: every sum has a fixed order, so results
  * are bit-identical run to run.  The radius, culling, binning and early-stop decisions of the forward are constants, as in gsplat.
  * NOT computed: gradients to viewmat / campos / K (gsplat's optional pose gradients; the reference leaves cam_rot_delta /
- * cam_trans_delta unused), cov_ignore=True (quaternion / scale input), packed mode, antialiased mode.
+ * cam_trans_delta unused), cov_ignore=True (quaternion / scale input), packed mode.
+ * Antialiased mode (rasterize_mode 1 above): stage 2 differentiates with respect to an entry's EFFECTIVE opacity
+ * opacities[g] * compensations[c,g]; stage 1 splits that into the opacity's share and the compensation's, whose gradient
+ * d comp / d Sigma2 = ((1 - comp^2) B^-1 - eps2d det(B^-1) I) / (2 comp)  (Sigma2 = J Cc J^T, B = Sigma2 + eps2d I, B^-1 the conic;
+ * exactly 0 where comp == 0) joins the conic's before the chain through J, the clamped mean, the rotation and the covariance.
  *
  * Stage 2 backward.  Takes the forward's projected arrays, its composite order (tile_offsets_out / flatten_ids_out and *n_isect of
  * v3a_gs_rasterize) and dL/d(out_color, out_depth, out_alpha); returns the gradient of every camera-Gaussian entry.  Each pixel
@@ -525,6 +534,8 @@ typedef struct {
   float* d_colors;          /* out [C,U,4] rgb + the depth channel */
   float* d_opacity_partial; /* out [C,U]: this camera's share of dL/d opacities[g] */
   void* workspace; long workspace_bytes;   /* v3a_gs_rasterize_backward_workspace_bytes(U, C, width, height, n_isect); too small: -4 */
+  const float* compensations;      /* as v3a_gs_rasterize had it ([C,U] or NULL); d_opacity_partial is then the gradient with
+                                      respect to opacities[g] * compensations[c,g] */
 } v3a_gs_rasterize_backward_args;
 long v3a_gs_rasterize_backward_workspace_bytes(long U, int C, int width, int height, long max_isect);
 int v3a_gs_rasterize_backward(const v3a_gs_rasterize_backward_args* a, void* stream);
@@ -549,7 +560,10 @@ typedef struct {
   float* d_means;           /* out [U,3] */
   float* d_covars;          /* out [U,3,3] */
   float* d_sh;              /* out, shape and layout of sh */
-  float* d_opacities;       /* out [U] */
+  float* d_opacities;       /* out [U]; mode 1: sum over c of d_opacity_partial[c,g] * comp[c,g], cameras in index order */
+  int rasterize_mode;       /* as v3a_gs_project had it; other than 0 / 1: -1 */
+  const float* opacities;   /* [U], mode 1 only (required there: NULL returns -1): dL/dcomp[c,g] = d_opacity_partial[c,g] * opacities[g].
+                               comp itself is recomputed from the scene, as everything else here, not read from memory */
 } v3a_gs_project_backward_args;
 int v3a_gs_project_backward(const v3a_gs_project_backward_args* a, void* stream);
 
@@ -769,6 +783,18 @@ typedef struct {
   double beta1, beta2, eps, bias_correction1, bias_correction2;
 } v3a_adam_args;
 int v3a_adam_step(const v3a_adam_args* a, void* stream);
+
+/* The post-optimisation loop's two regularisers (csrc/splat_reg.hip; simple_trainer.py:966-977): from opacity logits f32 [U] and
+ * log-scales f32 [U,3], out f64 [2] = (mean sigmoid(logit), mean exp(log_scale)) - the reference's abs() is the identity on both.
+ * fp64 after the loads; one partial pair per workgroup of a grid fixed by U, then a one-workgroup reduction in the order of
+ * csrc/fixed_sum.h: no atomics, bit-identical run to run.  workspace: v3a_splat_reg_workspace_bytes(U), 8-byte aligned (too small
+ * or misaligned: -4).  Backward (elementwise, every element written once, exactly linear in d_out f64 [2] on the device):
+ *   d_logits[i] = d_out[0] s (1 - s) / U,   d_log_scales[i] = d_out[1] exp(log_scale) / (3 U).
+ * 16-byte loads and stores with a scalar tail (all scalar for an array whose pointers are not 16-byte aligned). */
+long v3a_splat_reg_workspace_bytes(long U);   /* V3A_ERR_SHAPE for U < 1 or 3 U > 2^31 - 1 */
+int v3a_splat_reg(const float* logits, const float* log_scales, long U, double* out, void* workspace, long workspace_bytes, void* stream);
+int v3a_splat_reg_backward(const float* logits, const float* log_scales, long U, const double* d_out, float* d_logits,
+                           float* d_log_scales, void* stream);
 
 #ifdef __cplusplus
 }

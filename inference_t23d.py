@@ -64,9 +64,12 @@ def build_text_encoder(args, device):
     return make_pipeline_text_encoder(UMT5TextEncoder(UMT5Config(), sd, device=device), AutoTokenizer.from_pretrained(tk))
 
 
-def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False, eval_every=0, lpips=None):
+def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False, eval_every=0, lpips=None,
+           antialiased=False, random_bkgd=False, opacity_reg=0.0, scale_reg=0.0):
     """-> (refined Gaussians, stats or None).  With eval_every = K > 0 the views with index % K == 0 are held out of the loop and
-    scored before and after it: stats = {"before": {...}, "after": {...}, "held_out": [...]} (vist3a_amd.post_opt.evaluate_views)."""
+    scored before and after it: stats = {"before": {...}, "after": {...}, "held_out": [...]} (vist3a_amd.post_opt.evaluate_views).
+    antialiased / random_bkgd / opacity_reg / scale_reg: the PostOptConfig fields of those names; the evaluation renders in the
+    loop's rasterize mode."""
     from vist3a_amd import ops
     from vist3a_amd.post_opt import PostOptConfig, evaluate_views, post_optimize, train_views
     with torch.no_grad():
@@ -85,13 +88,15 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
         extra = dict(depths=depths, depth_masks=masks)
     cfg.use_bilateral_grid = bool(bilateral_grid)
     cfg.test_every = int(eval_every)
+    cfg.antialiased, cfg.random_bkgd = bool(antialiased), bool(random_bkgd)
+    cfg.opacity_reg, cfg.scale_reg = float(opacity_reg), float(scale_reg)
     ext, intr = pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach()
     stats = None
     if cfg.test_every > 0:
         train = set(train_views(frames.shape[0], cfg.test_every))      # raises when K leaves no view to train on
         held = [i for i in range(frames.shape[0]) if i not in train]
         score = lambda gs: evaluate_views(gs, frames[held].contiguous(), ext[held], intr[held], color_correct=cfg.use_bilateral_grid,
-                                          lpips=lpips)
+                                          lpips=lpips, antialiased=cfg.antialiased)
         stats = dict(before=score(gaussians), held_out=held)
     g, _ = post_optimize(gaussians, frames, ext, intr, cfg, steps=steps, **extra)
     if stats is not None:
@@ -121,6 +126,8 @@ def main(args):
     embeds = torch.load(args.text_embeds_path, map_location="cpu") if args.text_embeds_path else None
     if args.post_opt_eval_every < 0 or (args.post_opt_eval_every > 0 and args.post_opt_steps <= 0):
         raise ValueError("--post_opt_eval_every K needs K >= 0 and --post_opt_steps > 0 (it evaluates the views held out of the refinement)")
+    if args.post_opt_opacity_reg < 0 or args.post_opt_scale_reg < 0:
+        raise ValueError("--post_opt_opacity_reg and --post_opt_scale_reg are weights >= 0")
     if (args.lpips_vgg_weights is None) != (args.lpips_lin_weights is None):
         raise ValueError("--lpips_vgg_weights and --lpips_lin_weights go together: give both or neither")
     lpips = None
@@ -148,12 +155,21 @@ def main(args):
         g = out.gaussians
         if args.post_opt_steps > 0:   # against the frames the reconstruction saw, at the predicted context poses and intrinsics
             g, stats = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps, out.depth_dict,
-                              args.post_opt_depth_lambda, args.post_opt_bilateral_grid, args.post_opt_eval_every, lpips)
+                              args.post_opt_depth_lambda, args.post_opt_bilateral_grid, args.post_opt_eval_every, lpips,
+                              antialiased=args.post_opt_antialiased, random_bkgd=args.post_opt_random_bkgd,
+                              opacity_reg=args.post_opt_opacity_reg, scale_reg=args.post_opt_scale_reg)
             if stats is not None:
                 (save / "post_opt_stats.json").write_text(json.dumps(stats, indent=1))
         if not args.no_video:  # orbit video through the predicted context poses (reference :144-154)
-            save_interpolated_video(out.pred_context_pose["extrinsic"], out.pred_context_pose["intrinsic"], 1, args.feedforward_resolution,
-                                    args.feedforward_resolution, g, str(save), stitched.stitched_3d_model.decoder)
+            decoder = stitched.stitched_3d_model.decoder
+            mode = decoder.rasterize_mode
+            if args.post_opt_steps > 0 and args.post_opt_antialiased:   # a scene fitted in the antialiased mode is shown in it
+                decoder.rasterize_mode = "antialiased"
+            try:
+                save_interpolated_video(out.pred_context_pose["extrinsic"], out.pred_context_pose["intrinsic"], 1, args.feedforward_resolution,
+                                        args.feedforward_resolution, g, str(save), decoder)
+            finally:
+                decoder.rasterize_mode = mode
         export_ply(g.means[0], g.scales[0], g.rotations[0], g.harmonics[0], g.opacities[0], save / "gaussians.ply", save_sh_dc_only=True)
         print(f"[rank {rank}] {save}: {g.means.shape[1]} gaussians", flush=True)
     if world > 1:

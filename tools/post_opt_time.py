@@ -25,6 +25,7 @@ def main():
     ap.add_argument("--size", type=int, default=448)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--antialiased", action="store_true", help="the loop's renders in the rasteriser's antialiased mode")
     ap.add_argument("--bilateral_grid", action="store_true")
     a = ap.parse_args()
     from vist3a_amd import ops
@@ -51,7 +52,8 @@ def main():
         e[0].record()
         cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
         e[1].record()
-        col, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, view, campos, K, W, H, background=bg, clamp_rgb=True, workspace=ws)
+        col, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, view, campos, K, W, H, background=bg, clamp_rgb=True, workspace=ws,
+                                  rasterize_mode="antialiased" if a.antialiased else "classic")
         e[2].record()
         tv = None
         if grids is not None:

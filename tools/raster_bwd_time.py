@@ -26,6 +26,7 @@ def main():
     ap.add_argument("--size", type=int, default=448)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rasterize_mode", choices=("classic", "antialiased"), default="classic")
     a = ap.parse_args()
     from vist3a_amd import ops
     U, Cn, W, H = a.gaussians, a.cameras, a.size, a.size
@@ -53,7 +54,8 @@ def main():
     for it in range(a.warmup + a.iters):
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         e[0].record()
-        col, dep, alp = ops.gs_render(*lv, view, campos, K, W, H, background=bg, clamp_rgb=True, workspace=ws, n_isect_out=n_is)
+        col, dep, alp = ops.gs_render(*lv, view, campos, K, W, H, background=bg, clamp_rgb=True, workspace=ws, n_isect_out=n_is,
+                                      rasterize_mode=a.rasterize_mode)
         e[1].record()
         torch.autograd.backward([col, dep, alp], [wc, wd, wa])
         e[2].record()
@@ -67,7 +69,7 @@ def main():
     px = Cn * H * W
     f_bytes = n * (12 + 48) + Cn * U * 44 + U * 348 + px * 20
     b_bytes = n * (2 * 48 + 2 * 48) + Cn * U * (2 * 40 + 44 + 8) + px * 20 + 2 * U * 348
-    print(json.dumps(dict(gaussians=U, cameras=Cn, size=W, n_isect=n, forward_ms=round(f_ms, 3), backward_ms=round(b_ms, 3),
+    print(json.dumps(dict(gaussians=U, cameras=Cn, size=W, rasterize_mode=a.rasterize_mode, n_isect=n, forward_ms=round(f_ms, 3), backward_ms=round(b_ms, 3),
                           backward_over_forward=round(b_ms / f_ms, 2), row_buffer_bytes=48 * n,
                           forward_model_GBps=round(f_bytes / f_ms / 1e6, 1), backward_model_GBps=round(b_bytes / b_ms / 1e6, 1),
                           forward_vexp_bound_per_s=round(256 * n / (f_ms * 1e-3), -6),

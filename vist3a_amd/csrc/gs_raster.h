@@ -72,6 +72,7 @@ struct ProjEntry {
   float c00, c01, c02, c11, c12, c22;     // Cc = R S R^T (symmetric)
   float t00, t01, t02, t10, t11, t12;     // J Cc (t10: the backward's; dead in the forward)
   float q00, q01, q11, det;               // cov2d = J Cc J^T + eps2d, its determinant
+  float det_orig;                         // determinant of J Cc J^T itself: project_entry<true> only (antialiased mode), else 0
 };
 
 // world -> camera: V = view matrix (4x4 row-major), (mx, my, mz) = world mean
@@ -83,7 +84,10 @@ __host__ __device__ __forceinline__ void to_camera(const float* V, float mx, flo
 }
 
 // Kc = intrinsics (3x3), (x, y, z) = to_camera's mean, s.. = upper triangle of the world covariance.  No test is made here: near /
-// far (on z, before) and det > 0 (after) are the caller's.
+// far (on z, before) and det > 0 (after) are the caller's.  AA adds det_orig.  It is a template argument, and the classic callers
+// instantiate <false>, because lines that merely stand in the function - dead ones included - change how hipcc packs and contracts
+// the expressions of q00 / q01 / q11 / det (seen in the ISA), and with that the last bits of every classic output.
+template <bool AA = false>
 __host__ __device__ __forceinline__ ProjEntry project_entry(const float* V, const float* Kc, float W, float H, float eps2d, float x,
                                                             float y, float z, float s00, float s01, float s02, float s11, float s12,
                                                             float s22) {
@@ -110,8 +114,20 @@ __host__ __device__ __forceinline__ ProjEntry project_entry(const float* V, cons
   const float q01 = t01 * j11 + t02 * j12;
   const float q11 = t11 * j11 + t12 * j12 + eps2d;
   const float det = q00 * q11 - q01 * q01;
+  float det_orig = 0.f;
+  if constexpr (AA) {  // the un-blurred J Cc J^T from expressions of its own: q00 / q01 / q11 above stay as they are written
+    const float o00 = t00 * j00 + t02 * j02, o01 = t01 * j11 + t02 * j12, o11 = t11 * j11 + t12 * j12;
+    det_orig = o00 * o11 - o01 * o01;
+  }
   return {x, y, z, rz, rz2, fx, fy, cx, cy, lxp, lxn, lyp, lyn, tx, ty, j00, j02, j11, j12, c00, c01, c02, c11, c12, c22,
-          t00, t01, t02, t10, t11, t12, q00, q01, q11, det};
+          t00, t01, t02, t10, t11, t12, q00, q01, q11, det, det_orig};
+}
+
+// Antialiased mode (gsplat rasterize_mode="antialiased", the Mip-Splatting 2D filter): the blur widens a Gaussian AND dims it by
+// comp = sqrt(det(J Cc J^T) / det(J Cc J^T + eps2d I)), r = comp^2.  e from project_entry<true>, valid where e.det > 0.
+__host__ __device__ __forceinline__ float compensation(const ProjEntry& e, float& r) {
+  r = fmaxf(0.f, e.det_orig / e.det);
+  return sqrtf(r);
 }
 
 // ---------------------------------------------------------------------------------------------- tiles
@@ -169,13 +185,16 @@ __host__ __device__ __forceinline__ float fast_exp(float x) {
 
 // Stage one Gaussian of a tile list into LDS as three 16-byte records {x, y, opacity, -} {conic a, b, c, -} {r, g, b, depth}.
 // id = camera-major entry index c*U + g; an id outside the call reads as transparent (never the case for the forward's own sort).
-// P has means2d, conics, colors, opac, U and CU = C * U.
+// P has means2d, conics, colors, opac, comp, U and CU = C * U.  comp = the entries' antialiasing compensations [C,U] or null
+// (classic: no load): the staged opacity is opac[g] * comp[id], one multiply, here and nowhere else, so both passes see one alpha.
 template <class P>
 __device__ __forceinline__ void stage_gaussian(const P& p, unsigned int id, int cam, f32x4* dst) {
   f32x4 a = {0.f, 0.f, 0.f, 0.f}, c = a, col = a;
   const unsigned int gi = id - (unsigned int)cam * (unsigned int)p.U;
   if (id < p.CU && gi < (unsigned int)p.U) {
-    a = f32x4{p.means2d[2L * id], p.means2d[2L * id + 1], p.opac[gi], 0.f};
+    float o = p.opac[gi];
+    if (p.comp) o *= p.comp[id];
+    a = f32x4{p.means2d[2L * id], p.means2d[2L * id + 1], o, 0.f};
     c = f32x4{p.conics[3L * id], p.conics[3L * id + 1], p.conics[3L * id + 2], 0.f};
     col = *(const f32x4*)(p.colors + 4L * id);
   }
@@ -237,6 +256,7 @@ int check_sh_args(const A& a) {
   if (a.U < 0 || a.C <= 0 || a.width <= 0 || a.height <= 0 || a.U >= (1L << 31)) return V3A_ERR_SHAPE;
   if (a.sh_degree < 0 || a.sh_degree > 4 || a.sh_k < (a.sh_degree + 1) * (a.sh_degree + 1) || a.sh_k > 64) return V3A_ERR_SHAPE;
   if (a.sh_layout != 0 && a.sh_layout != 1) return V3A_ERR_ARG;
+  if (a.rasterize_mode != 0 && a.rasterize_mode != 1) return V3A_ERR_ARG;
   return V3A_OK;
 }
 
@@ -250,6 +270,16 @@ void dispatch_sh_degree(int deg, F&& f) {
     case 3: f(std::integral_constant<int, 3>{}); break;
     default: f(std::integral_constant<int, 4>{}); break;
   }
+}
+
+// f(degree as above, std::bool_constant<antialiased>): rasterize_mode 0 or 1 (checked by check_sh_args).  The mode is a template
+// argument of the backward projection kernel so that its classic instantiations hold no trace of the other one.
+template <class F>
+void dispatch_sh_degree_mode(int deg, int mode, F&& f) {
+  dispatch_sh_degree(deg, [&](auto d) {
+    if (mode) f(d, std::true_type{});
+    else f(d, std::false_type{});
+  });
 }
 
 // The projection kernels of both directions: one wave per 64 Gaussians, their SH rows (3 * sh_k floats each) in dynamic LDS

@@ -5,7 +5,9 @@
 //   v3a_gs_project    one wave per 64 Gaussians, ALL C cameras of the batch: the 64 x 300-B SH block is staged once into
 //                     LDS with coalesced 16-B loads (it is 75 % of the input bytes) and mean/covariance are held in
 //                     registers while the wave loops over cameras: world->camera, EWA projection of the 3x3 covariance,
-//                     +eps2d blur, conic, 3-sigma radius, near/far/screen culling, SH colour for survivors.
+//                     +eps2d blur, conic, 3-sigma radius, near/far/screen culling, SH colour for survivors.  With
+//                     rasterize_mode 1 (gsplat's "antialiased") a second small kernel writes the opacity compensation of
+//                     every entry, which v3a_gs_rasterize multiplies into the opacity as it stages a Gaussian.
 //   v3a_gs_rasterize  tile counts -> rocPRIM scan -> (camera | tile | depth bits) keys -> rocPRIM stable radix sort ->
 //                     tile ranges -> one 256-lane workgroup per 16x16 tile of every camera (C x tiles workgroups fill the
 //                     256 CUs where one camera's ~800 tiles cannot): Gaussians staged through LDS 256 at a time, read back
@@ -94,6 +96,38 @@ __global__ __launch_bounds__(64) void gs_project_kernel(ProjP p) {
   }
 }
 
+// Antialiased mode: the opacity compensation of every entry, 0 for a culled one.  A kernel of its own AFTER the classic projection
+// (it reads that kernel's radii), one lane per Gaussian looping over the cameras with mean and covariance in registers: the mode's
+// radii / means2d / conics / colours are then the classic kernel's by construction, bit for bit, and classic calls run what they
+// always ran.  The price is a second read of means and covars (48 of the ~350 bytes per Gaussian the projection moves).
+struct CompP {
+  const float* means; const float* covars; const float* viewmat; const float* K; const int* radii;
+  int U, C, W, H;
+  float eps2d;
+  float* comp;
+};
+
+__global__ __launch_bounds__(256) void gs_compensation_kernel(CompP p) {
+  const int g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= p.U) return;
+  const float mx = p.means[3L * g], my = p.means[3L * g + 1], mz = p.means[3L * g + 2];
+  const float* cv = p.covars + 9L * g;
+  const float s00 = cv[0], s01 = cv[1], s02 = cv[2], s11 = cv[4], s12 = cv[5], s22 = cv[8];
+  for (int c = 0; c < p.C; ++c) {
+    const long o = (long)c * p.U + g;
+    float comp = 0.f;
+    if (p.radii[o] > 0) {  // inside near / far and det > 0, or the projection would have culled it
+      const float* V = p.viewmat + 16 * c;
+      float x, y, z;
+      to_camera(V, mx, my, mz, x, y, z);
+      const ProjEntry e = project_entry<true>(V, p.K + 9 * c, (float)p.W, (float)p.H, p.eps2d, x, y, z, s00, s01, s02, s11, s12, s22);
+      float r;
+      comp = compensation(e, r);
+    }
+    p.comp[o] = comp;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- binning
 struct BinP {
   const int* radii; const float* means2d; const float* depths;
@@ -137,7 +171,7 @@ __global__ __launch_bounds__(256) void gs_ranges_kernel(BinP p) {
 
 // ---------------------------------------------------------------------------------------------- compositing
 struct BlendP {
-  const float* means2d; const float* conics; const float* colors; const float* opac;
+  const float* means2d; const float* conics; const float* colors; const float* opac; const float* comp;
   const unsigned int* offs; const unsigned int* ids;
   const float* bg;
   float* out_color; float* out_depth; float* out_alpha;
@@ -190,10 +224,15 @@ extern "C" int v3a_gs_project(const v3a_gs_project_args* a, void* stream) {
       !a->conics || !a->colors)
     return V3A_ERR_ARG;
   if (const int rc = check_sh_args(*a)) return rc;
+  if (a->rasterize_mode == 1 && !a->compensations) return V3A_ERR_ARG;
   if (a->U == 0) return V3A_OK;
   ProjP p = {a->means, a->covars, a->sh, a->viewmat, a->campos, a->K, a->sh_layout, a->sh_k, a->sh_degree, (int)a->U, a->C, a->width,
              a->height, a->near_plane, a->far_plane, a->radius_clip, a->eps2d, a->radii, a->means2d, a->depths, a->conics, a->colors};
   dispatch_sh_degree(a->sh_degree, [&](auto d) { launch_sh_waves(gs_project_kernel<decltype(d)::value>, p, (hipStream_t)stream); });
+  if (a->rasterize_mode == 1) {
+    CompP cp = {a->means, a->covars, a->viewmat, a->K, a->radii, (int)a->U, a->C, a->width, a->height, a->eps2d, a->compensations};
+    hipLaunchKernelGGL(gs_compensation_kernel, dim3((unsigned)((a->U + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cp);
+  }
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
@@ -249,7 +288,7 @@ extern "C" int v3a_gs_rasterize(const v3a_gs_rasterize_args* a, void* stream_) {
   if (a->flatten_ids_out && n > 0 &&
       hipMemcpyAsync(a->flatten_ids_out, ids, 4 * (size_t)n, hipMemcpyDeviceToDevice, stream) != hipSuccess)
     return V3A_ERR_LAUNCH;
-  BlendP bp = {a->means2d, a->conics, a->colors, a->opacities, b.offs, ids, a->background, a->out_color, a->out_depth, a->out_alpha,
+  BlendP bp = {a->means2d, a->conics, a->colors, a->opacities, a->compensations, b.offs, ids, a->background, a->out_color, a->out_depth, a->out_alpha,
                (unsigned int)CU, (int)a->U, a->width, a->height, tg.tw, tg.ntiles, a->clamp_rgb};
   hipLaunchKernelGGL(gs_blend_kernel, dim3((unsigned)nt_all), dim3(256), 0, stream, bp);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;

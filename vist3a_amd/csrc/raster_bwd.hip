@@ -1,6 +1,6 @@
 // Backward of the 3D-Gaussian rasteriser (raster.hip) for gfx950, fp32: what gsplat's rasterize_to_pixels_bwd +
 // fully_fused_projection_bwd + spherical_harmonics_bwd give torch.autograd, for the same call the forward replaces
-// (RGB+D, classic, packed=False, explicit world covariances).  Gradients reach means, covars, sh and opacities; cameras are constants.
+// (RGB+D, classic or antialiased, packed=False, explicit world covariances).  Gradients reach means, covars, sh and opacities; cameras are constants.
 //
 //   v3a_gs_rasterize_backward   count + rocPRIM scan (the forward's, re-run: each camera-Gaussian entry's first row slot) ->
 //                               gs_blend_bwd_kernel, one 256-lane workgroup per 16x16 tile of every camera: walks the tile's
@@ -11,7 +11,9 @@
 //                               gs_rowsum_kernel adds an entry's rows in slot order.
 //   v3a_gs_project_backward     one wave per 64 Gaussians looping over the cameras in index order (as the forward): conic ->
 //                               2D covariance -> J, camera covariance -> world covariance; mean through J, the pixel mean,
-//                               the depth channel and the SH view direction; SH coefficients.
+//                               the depth channel and the SH view direction; SH coefficients.  Antialiased mode: the entry's
+//                               dL/d(opacity * comp) splits into the opacity's share (x comp) and dL/dcomp (x opacity), which
+//                               enters the 2D covariance's gradient beside the conic's; comp is recomputed, not read.
 // No atomics on floats anywhere: every sum has a fixed order, results are bit-identical run to run.
 #include "common.h"
 #include "gs_raster.h"
@@ -63,7 +65,7 @@ __host__ __device__ __forceinline__ void blend_bwd_pair(float dx, float dy, floa
 
 // ---------------------------------------------------------------------------------------------- blend backward
 struct BlendBwdP {
-  const int* radii; const float* means2d; const float* conics; const float* colors; const float* opac;
+  const int* radii; const float* means2d; const float* conics; const float* colors; const float* opac; const float* comp;
   const unsigned int* offs; const unsigned int* ids; const unsigned int* counts; const unsigned int* incl;
   const float* bg; const float* d_color; const float* d_depth; const float* d_alpha;
   float* rows;
@@ -285,11 +287,12 @@ struct ProjGeo {  // what the forward derives from the call's constants
 
 // One visible (camera, Gaussian) entry.  m = world mean, sw = upper triangle of the world covariance (00 01 02 11 12 22),
 // s = this Gaussian's SH row, vm2 / vcon / vcol = the entry's incoming gradients.  Adds into vm[3], vS[6] (symmetric dL/dS of the
-// full matrix, same packing) and dsh[3 * NB] (basis-major: dsh[3 k + channel]).
-template <int DEG>
-__host__ __device__ __forceinline__ void proj_bwd_entry(const ProjGeo& q, const float* m, const float* sw, const float* s, int sh_layout,
-                                                        int sh_k, const float* vm2, const float* vcon, const float* vcol, float* vm,
-                                                        float* vS, float* dsh) {
+// full matrix, same packing) and dsh[3 * NB] (basis-major: dsh[3 k + channel]).  AA (antialiased mode): vop_eff = the entry's
+// dL/d(effective opacity), opac = the Gaussian's opacity; returns comp, and dL/dcomp = vop_eff * opac joins the conic's dL/dQ.
+template <int DEG, bool AA>
+__host__ __device__ __forceinline__ float proj_bwd_entry(const ProjGeo& q, const float* m, const float* sw, const float* s, int sh_layout,
+                                                         int sh_k, const float* vm2, const float* vcon, const float* vcol, float vop_eff,
+                                                         float opac, float* vm, float* vS, float* dsh) {
   constexpr int NB = (DEG + 1) * (DEG + 1);
   const float* V = q.V;
   const float R00 = V[0], R01 = V[1], R02 = V[2], R10 = V[4], R11 = V[5], R12 = V[6], R20 = V[8], R21 = V[9], R22 = V[10];
@@ -297,7 +300,7 @@ __host__ __device__ __forceinline__ void proj_bwd_entry(const ProjGeo& q, const 
   // the forward's chain up to the 2D covariance
   float x, y, z;
   to_camera(V, mx, my, mz, x, y, z);
-  const ProjEntry e = project_entry(V, q.Kc, q.W, q.H, q.eps2d, x, y, z, sw[0], sw[1], sw[2], sw[3], sw[4], sw[5]);
+  const ProjEntry e = project_entry<AA>(V, q.Kc, q.W, q.H, q.eps2d, x, y, z, sw[0], sw[1], sw[2], sw[3], sw[4], sw[5]);
   const float rz = e.rz, rz2 = e.rz2, fx = e.fx, fy = e.fy, tx = e.tx, ty = e.ty;
   const float lxp = e.lxp, lxn = e.lxn, lyp = e.lyp, lyn = e.lyn, j00 = e.j00, j02 = e.j02, j11 = e.j11, j12 = e.j12;
   const float t00 = e.t00, t01 = e.t01, t02 = e.t02, t10 = e.t10, t11 = e.t11, t12 = e.t12;
@@ -308,7 +311,17 @@ __host__ __device__ __forceinline__ void proj_bwd_entry(const ProjGeo& q, const 
   // conic = Q^-1:  dL/dQ = -X G X with G = [[va, vb/2], [vb/2, vc]]  (symmetric 2x2; M01 stands for both off-diagonal positions)
   const float G00 = vcon[0], G01 = 0.5f * vcon[1], G11 = vcon[2];
   const float h00 = X00 * G00 + X01 * G01, h01 = X00 * G01 + X01 * G11, h10 = X01 * G00 + X11 * G01, h11 = X01 * G01 + X11 * G11;
-  const float M00 = -(h00 * X00 + h01 * X01), M01 = -(h00 * X01 + h01 * X11), M11 = -(h10 * X01 + h11 * X11);
+  float M00 = -(h00 * X00 + h01 * X01), M01 = -(h00 * X01 + h01 * X11), M11 = -(h10 * X01 + h11 * X11);
+  float comp = 1.f;
+  if constexpr (AA) {
+    // comp = sqrt(r), r = det(Q - eps I) / det(Q):  dr/dQ = (1 - r) X - eps det(X) I,  dcomp/dQ = dr/dQ / (2 comp); exactly 0 at comp == 0
+    float r;
+    comp = compensation(e, r);
+    if (comp > 0.f) {
+      const float k = (vop_eff * opac) / (2.f * comp), omr = 1.f - r, ed = q.eps2d * id;  // det(X) = 1 / det(Q)
+      M00 += k * (omr * X00 - ed); M01 += k * (omr * X01); M11 += k * (omr * X11 - ed);
+    }
+  }
   // Q = J Cc J^T + eps:  dL/dCc = J^T M J (symmetric 3x3),  dL/dJ = 2 M (J Cc)
   const float w00 = j00 * j00 * M00, w01 = j00 * j11 * M01, w02 = j00 * (M00 * j02 + M01 * j12);
   const float w11 = j11 * j11 * M11, w12 = j11 * (M01 * j02 + M11 * j12);
@@ -350,6 +363,7 @@ __host__ __device__ __forceinline__ void proj_bwd_entry(const ProjGeo& q, const 
   sh_eval_bwd<DEG>(ux, uy, uz, gk, vux, vuy, vuz);
   const float dot = ux * vux + uy * vuy + uz * vuz;  // u = d / |d|:  dL/dd = (v - u (u . v)) / |d|
   if (nrm >= 1e-20f) { vm[0] += (vux - ux * dot) * inv; vm[1] += (vuy - uy * dot) * inv; vm[2] += (vuz - uz * dot) * inv; }
+  return comp;
 }
 
 struct ProjBwdP {
@@ -359,12 +373,13 @@ struct ProjBwdP {
   int U, C, W, H;
   float eps2d;
   const int* radii; const float* d_means2d; const float* d_conics; const float* d_colors; const float* d_opac;
+  const float* opac;  // antialiased mode only: [U]
   float* d_means; float* d_covars; float* d_sh; float* d_opacities;
 };
 
 // One wave = 64 consecutive Gaussians, cameras in index order.  LDS: the SH rows of the 64 Gaussians (as the forward stages them),
 // overwritten at the end by their gradient rows for a coalesced store.
-template <int DEG>
+template <int DEG, bool AA>
 __global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
   extern __shared__ float s_sh[];
   constexpr int NB = (DEG + 1) * (DEG + 1);
@@ -385,6 +400,8 @@ __global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
     const float m[3] = {p.means[3L * g], p.means[3L * g + 1], p.means[3L * g + 2]};
     const float* cv = p.covars + 9L * g;
     const float sw[6] = {cv[0], cv[1], cv[2], cv[4], cv[5], cv[8]};
+    float opac = 0.f;
+    if constexpr (AA) opac = p.opac[g];
     for (int c = 0; c < p.C; ++c) {
       const long o = (long)c * p.U + g;
       if (p.radii[o] <= 0) continue;  // culled entries contribute exactly zero
@@ -393,8 +410,10 @@ __global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
       const float vcon[3] = {p.d_conics[3 * o], p.d_conics[3 * o + 1], p.d_conics[3 * o + 2]};
       const f32x4 vc4 = *(const f32x4*)(p.d_colors + 4 * o);
       const float vcol[4] = {vc4[0], vc4[1], vc4[2], vc4[3]};
-      proj_bwd_entry<DEG>(q, m, sw, s, p.sh_layout, p.sh_k, vm2, vcon, vcol, vm, vS, dsh);
-      vop += p.d_opac[o];
+      const float vo = p.d_opac[o];
+      const float comp = proj_bwd_entry<DEG, AA>(q, m, sw, s, p.sh_layout, p.sh_k, vm2, vcon, vcol, vo, opac, vm, vS, dsh);
+      if constexpr (AA) vop += vo * comp;
+      else vop += vo;
     }
     p.d_means[3L * g] = vm[0]; p.d_means[3L * g + 1] = vm[1]; p.d_means[3L * g + 2] = vm[2];
     float* dc = p.d_covars + 9L * g;  // "the upper triangle is used": an off-diagonal entry carries both symmetric positions
@@ -441,7 +460,7 @@ extern "C" int v3a_gs_rasterize_backward(const v3a_gs_rasterize_backward_args* a
   float* rows = (float*)(ws + l.rows);
   const unsigned gb = (unsigned)((CU + 255) / 256);
   if (!count_and_scan({a->radii, a->means2d, CU, tg.tw, tg.th, counts}, incl, ws + l.tmp, l.tmp_bytes, stream)) return V3A_ERR_LAUNCH;
-  BlendBwdP bp = {a->radii, a->means2d, a->conics, a->colors, a->opacities, a->tile_offsets, a->flatten_ids, counts, incl, a->background,
+  BlendBwdP bp = {a->radii, a->means2d, a->conics, a->colors, a->opacities, a->compensations, a->tile_offsets, a->flatten_ids, counts, incl, a->background,
                   a->d_color, a->d_depth, a->d_alpha, rows, (unsigned int)a->n_isect, (unsigned int)CU, (int)a->U, a->width, a->height,
                   tg.tw, tg.th, tg.ntiles, a->clamp_rgb};
   if (a->n_isect > 0) hipLaunchKernelGGL(gs_blend_bwd_kernel, dim3((unsigned)(tg.ntiles * a->C)), dim3(256), 0, stream, bp);
@@ -455,10 +474,13 @@ extern "C" int v3a_gs_project_backward(const v3a_gs_project_backward_args* a, vo
       !a->d_colors || !a->d_opacity_partial || !a->d_means || !a->d_covars || !a->d_sh || !a->d_opacities)
     return V3A_ERR_ARG;
   if (const int rc = check_sh_args(*a)) return rc;
+  if (a->rasterize_mode == 1 && !a->opacities) return V3A_ERR_ARG;
   if (a->U == 0) return V3A_OK;
   ProjBwdP p = {a->means, a->covars, a->sh, a->viewmat, a->campos, a->K, a->sh_layout, a->sh_k, (int)a->U, a->C, a->width, a->height,
-                a->eps2d, a->radii, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial, a->d_means, a->d_covars, a->d_sh,
+                a->eps2d, a->radii, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial, a->opacities, a->d_means, a->d_covars, a->d_sh,
                 a->d_opacities};
-  dispatch_sh_degree(a->sh_degree, [&](auto d) { launch_sh_waves(gs_project_bwd_kernel<decltype(d)::value>, p, (hipStream_t)stream); });
+  dispatch_sh_degree_mode(a->sh_degree, a->rasterize_mode, [&](auto d, auto aa) {
+    launch_sh_waves(gs_project_bwd_kernel<decltype(d)::value, decltype(aa)::value>, p, (hipStream_t)stream);
+  });
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

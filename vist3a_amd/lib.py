@@ -77,6 +77,7 @@ class GsProjectArgs(C.Structure):
         ("U", C.c_long), ("C", C.c_int), ("width", C.c_int), ("height", C.c_int),
         ("near_plane", C.c_float), ("far_plane", C.c_float), ("radius_clip", C.c_float), ("eps2d", C.c_float),
         ("radii", C.c_void_p), ("means2d", C.c_void_p), ("depths", C.c_void_p), ("conics", C.c_void_p), ("colors", C.c_void_p),
+        ("rasterize_mode", C.c_int), ("compensations", C.c_void_p),   # trailing: zero-filled = classic
     ]
 
 
@@ -101,6 +102,7 @@ class GsRasterizeArgs(C.Structure):
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_long), ("max_isect", C.c_long),
         ("n_isect", C.POINTER(C.c_long)),
         ("tile_offsets_out", C.c_void_p), ("flatten_ids_out", C.c_void_p),
+        ("compensations", C.c_void_p),
     ]
 
 
@@ -113,6 +115,7 @@ class GsRasterizeBackwardArgs(C.Structure):
         ("d_color", C.c_void_p), ("d_depth", C.c_void_p), ("d_alpha", C.c_void_p),
         ("d_means2d", C.c_void_p), ("d_conics", C.c_void_p), ("d_colors", C.c_void_p), ("d_opacity_partial", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+        ("compensations", C.c_void_p),
     ]
 
 
@@ -125,8 +128,8 @@ class GsProjectBackwardArgs(C.Structure):
         ("radii", C.c_void_p),
         ("d_means2d", C.c_void_p), ("d_conics", C.c_void_p), ("d_colors", C.c_void_p), ("d_opacity_partial", C.c_void_p),
         ("d_means", C.c_void_p), ("d_covars", C.c_void_p), ("d_sh", C.c_void_p), ("d_opacities", C.c_void_p),
+        ("rasterize_mode", C.c_int), ("opacities", C.c_void_p),
     ]
-
 
 
 class AttnArgs(C.Structure):
@@ -388,10 +391,13 @@ SYMBOLS = {
     "v3a_splat_activate": (C.c_int, [C.c_void_p] * 3 + [C.c_long] + [C.c_void_p] * 3),
     "v3a_splat_activate_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),
     "v3a_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
+    "v3a_splat_reg_workspace_bytes": (C.c_long, [C.c_long]),
+    "v3a_splat_reg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
+    "v3a_splat_reg_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 4),
 }
 
 _lib = None
-EXPECTED_ABI = 29   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 30   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

@@ -10,7 +10,10 @@ width, the world covariances are passed explicitly, background = cfg.background_
 Differentiable like gsplat's renderer: when grad mode is on and any of `gaussians.means / covariances / harmonics / opacities`
 requires grad, the camera batches go through `ops.gs_render` (HIP backward kernels, csrc/raster_bwd.hip) and color / depth / alpha
 carry the graph back to the Gaussians.  The forward values are the same kernels' either way.  Cameras are constants: extrinsics or
-intrinsics that require grad raise NotImplementedError (gsplat's optional pose gradients are not implemented)."""
+intrinsics that require grad raise NotImplementedError (gsplat's optional pose gradients are not implemented).
+
+An extension: `rasterize_mode="antialiased"` renders (and differentiates) with gsplat's mode of that name; the reference's decoder
+hard-codes "classic", which stays the default."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -33,7 +36,10 @@ class DecoderOutput:
 
 class DecoderSplattingCUDA:
     def __init__(self, background_color: Sequence[float] = (1.0, 1.0, 1.0), make_scale_invariant: bool = False, device="cuda",
-                 camera_batch: int = 12):
+                 camera_batch: int = 12, rasterize_mode: str = "classic"):
+        if rasterize_mode not in ops.RASTERIZE_MODES:
+            raise ValueError(f"rasterize_mode must be one of {sorted(ops.RASTERIZE_MODES)}, got {rasterize_mode!r}")
+        self.rasterize_mode = rasterize_mode
         self.camera_batch = camera_batch  # cameras per rasteriser launch (scratch = camera_batch * U * 44 B + sort buffers)
         self.make_scale_invariant = make_scale_invariant
         self.device = torch.device(device)
@@ -74,13 +80,14 @@ class DecoderSplattingCUDA:
                 if need_grad:
                     c_, d_, a_ = ops.gs_render(means, cov, sh, op, w2c_d[sl].contiguous(), cam_d[sl].contiguous(), K_d[sl].contiguous(),
                                                W, H, sh_degree=sh_degree, sh_layout=1, background=self.background_color, clamp_rgb=True,
-                                               workspace=self._ws, n_isect_out=self.last_n_isect)
+                                               workspace=self._ws, n_isect_out=self.last_n_isect, rasterize_mode=self.rasterize_mode)
                     ci.append(c_.permute(0, 3, 1, 2))
                     di.append(d_)
                     ai.append(a_)
                     continue
                 pr = ops.gs_project(means, cov, sh, w2c_d[sl].contiguous(), cam_d[sl].contiguous(), K_d[sl].contiguous(), W, H,
-                                    sh_degree=sh_degree, sh_layout=1, near_plane=1e-10, far_plane=1e10, radius_clip=0.1, eps2d=0.3)
+                                    sh_degree=sh_degree, sh_layout=1, near_plane=1e-10, far_plane=1e10, radius_clip=0.1, eps2d=0.3,
+                                    rasterize_mode=self.rasterize_mode)
                 r = ops.gs_rasterize(pr, op, W, H, background=self.background_color, clamp_rgb=True, workspace=self._ws)
                 self.last_n_isect.append(r["n_isect"])
                 ci.append(r["color"].permute(0, 3, 1, 2))

@@ -984,21 +984,38 @@ def _gs_scene_args(means, covars, sh, viewmat, campos, K, sh_layout):
     return Cn, means.shape[0], sh.shape[2] if sh_layout == 1 else sh.shape[1]
 
 
+RASTERIZE_MODES = {"classic": 0, "antialiased": 1}   # gsplat's rasterize_mode -> the C ABI's
+
+
+def _gs_mode(rasterize_mode: str) -> int:
+    if rasterize_mode not in RASTERIZE_MODES:
+        raise ValueError(f"rasterize_mode must be one of {sorted(RASTERIZE_MODES)}, got {rasterize_mode!r}")
+    return RASTERIZE_MODES[rasterize_mode]
+
+
 def gs_project(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, viewmat: torch.Tensor, campos: torch.Tensor,
                K: torch.Tensor, width: int, height: int, *, sh_degree: int = 4, sh_layout: int = 1, near_plane: float = 1e-10,
-               far_plane: float = 1e10, radius_clip: float = 0.1, eps2d: float = 0.3):
+               far_plane: float = 1e10, radius_clip: float = 0.1, eps2d: float = 0.3, rasterize_mode: str = "classic"):
     """fully_fused_projection + SH colours for C cameras at once (viewmat [C,4,4], campos [C,3], K [C,3,3] -> outputs [C,U,...])
-    or one camera (viewmat [4,4] -> outputs [U,...]).  sh: [U,3,K] (sh_layout=1, Gaussians.harmonics) or [U,K,3] (0)."""
+    or one camera (viewmat [4,4] -> outputs [U,...]).  sh: [U,3,K] (sh_layout=1, Gaussians.harmonics) or [U,K,3] (0).
+    rasterize_mode="antialiased" adds `compensations` [C,U] to the dict (gs_rasterize and gs_rasterize_backward pick it up from
+    there): each entry's opacity factor sqrt(det(cov2d) / det(cov2d + eps2d I)); every other output is the classic one."""
+    mode = _gs_mode(rasterize_mode)
     Cn, U, sh_k = _gs_scene_args(means, covars, sh, viewmat, campos, K, sh_layout)
     dev = means.device
     lead = () if viewmat.dim() == 2 else (Cn,)
     radii = torch.empty(*lead, U, device=dev, dtype=torch.int32)
     e = lambda *s: torch.empty(*lead, *s, device=dev, dtype=f32)
     m2, dep, con, col = e(U, 2), e(U), e(U, 3), e(U, 4)
+    comp = e(U) if mode else None
     a = L.GsProjectArgs(_ptr(means), _ptr(covars), _ptr(sh), sh_layout, sh_k, sh_degree, _ptr(viewmat), _ptr(campos), _ptr(K), U, Cn,
-                        width, height, near_plane, far_plane, radius_clip, eps2d, _ptr(radii), _ptr(m2), _ptr(dep), _ptr(con), _ptr(col))
+                        width, height, near_plane, far_plane, radius_clip, eps2d, _ptr(radii), _ptr(m2), _ptr(dep), _ptr(con), _ptr(col),
+                        mode, _ptr(comp))
     L.check(L.load().v3a_gs_project(C.byref(a), _stream()), "v3a_gs_project")
-    return dict(radii=radii, means2d=m2, depths=dep, conics=con, colors=col)
+    out = dict(radii=radii, means2d=m2, depths=dep, conics=con, colors=col)
+    if mode:
+        out["compensations"] = comp
+    return out
 
 
 class _GsScratch:
@@ -1032,7 +1049,8 @@ class GsWorkspace(_GsScratch):
 def gs_rasterize(proj: dict, opacities: torch.Tensor, width: int, height: int, *, background: Optional[torch.Tensor] = None,
                  clamp_rgb: bool = True, workspace: Optional[GsWorkspace] = None, return_order: bool = False):
     """isect_tiles + sort + rasterize_to_pixels for the cameras of `proj` -> dict(color [C,H,W,3], depth [C,H,W], alpha [C,H,W],
-    n_isect); without the C axis when `proj` came from a single-camera gs_project call."""
+    n_isect); without the C axis when `proj` came from a single-camera gs_project call.  A `proj` of the antialiased mode carries
+    its compensations: entry (c, g) then draws with opacities[g] * compensations[c, g]."""
     U, dev = opacities.shape[0], opacities.device
     if opacities.dtype != f32 or not opacities.is_contiguous():
         raise ValueError("opacities: contiguous fp32 [U] required")
@@ -1041,6 +1059,9 @@ def gs_rasterize(proj: dict, opacities: torch.Tensor, width: int, height: int, *
     single = proj["radii"].dim() == 1
     Cn = 1 if single else proj["radii"].shape[0]
     lead = () if single else (Cn,)
+    comp = proj.get("compensations")
+    if comp is not None:
+        _gs_f32(comp, "compensations", Cn * U)
     wsp = workspace or GsWorkspace()
     color = torch.empty(*lead, height, width, 3, device=dev, dtype=f32)
     depth = torch.empty(*lead, height, width, device=dev, dtype=f32)
@@ -1055,7 +1076,7 @@ def gs_rasterize(proj: dict, opacities: torch.Tensor, width: int, height: int, *
         a = L.GsRasterizeArgs(_ptr(proj["radii"]), _ptr(proj["means2d"]), _ptr(proj["depths"]), _ptr(proj["conics"]), _ptr(proj["colors"]),
                               _ptr(opacities), _ptr(background) if background is not None else None, U, Cn, width, height, int(clamp_rgb),
                               _ptr(color), _ptr(depth), _ptr(alpha), _ptr(buf), buf.numel(), wsp.cap, C.pointer(n_host),
-                              _ptr(offs) if return_order else None, _ptr(ids) if return_order else None)
+                              _ptr(offs) if return_order else None, _ptr(ids) if return_order else None, _ptr(comp))
         rc = L.load().v3a_gs_rasterize(C.byref(a), _stream())
         if rc == -4:  # V3A_ERR_WORKSPACE: the count is known now, grow once and redo
             need = n_host.value
@@ -1087,7 +1108,8 @@ def gs_rasterize_backward(proj: dict, opacities: torch.Tensor, width: int, heigh
                           workspace: Optional[GsBwdWorkspace] = None):
     """Backward of gs_rasterize: `proj` and (tile_offsets, flatten_ids) as the forward had / returned them (return_order=True),
     d_color [C,H,W,3], d_depth, d_alpha [C,H,W] -> dict(d_means2d [C,U,2], d_conics [C,U,3], d_colors [C,U,4], d_opacity [C,U])
-    per camera-Gaussian entry; without the C axis when `proj` came from a single-camera gs_project call."""
+    per camera-Gaussian entry; without the C axis when `proj` came from a single-camera gs_project call.  With compensations in
+    `proj` (antialiased mode) d_opacity is the gradient with respect to the entry's opacities[g] * compensations[c, g]."""
     U, dev = opacities.shape[0], opacities.device
     if U == 0:
         raise ValueError("no Gaussians to draw")
@@ -1105,6 +1127,9 @@ def gs_rasterize_backward(proj: dict, opacities: torch.Tensor, width: int, heigh
     _gs_f32(d_alpha, "d_alpha", Cn * height * width)
     if background is not None:
         _gs_f32(background, "background", 3)
+    comp = proj.get("compensations")
+    if comp is not None:
+        _gs_f32(comp, "compensations", Cn * U)
     if tile_offsets.dtype != torch.int32 or not tile_offsets.is_contiguous() or tile_offsets.numel() != Cn * ntiles + 1:
         raise ValueError(f"tile_offsets: contiguous int32 [{Cn * ntiles + 1}] required")
     if flatten_ids.dtype != torch.int32 or not flatten_ids.is_contiguous():
@@ -1117,18 +1142,25 @@ def gs_rasterize_backward(proj: dict, opacities: torch.Tensor, width: int, heigh
     a = L.GsRasterizeBackwardArgs(_ptr(proj["radii"]), _ptr(proj["means2d"]), _ptr(proj["conics"]), _ptr(proj["colors"]), _ptr(opacities),
                                   _ptr(background) if background is not None else None, U, Cn, width, height, int(clamp_rgb),
                                   _ptr(tile_offsets), _ptr(flatten_ids) if n_isect else None, n_isect, _ptr(d_color), _ptr(d_depth),
-                                  _ptr(d_alpha), _ptr(dm2), _ptr(dcon), _ptr(dcol), _ptr(dop), _ptr(buf), buf.numel())
+                                  _ptr(d_alpha), _ptr(dm2), _ptr(dcon), _ptr(dcol), _ptr(dop), _ptr(buf), buf.numel(), _ptr(comp))
     L.check(L.load().v3a_gs_rasterize_backward(C.byref(a), _stream()), "v3a_gs_rasterize_backward")
     return dict(d_means2d=dm2, d_conics=dcon, d_colors=dcol, d_opacity=dop)
 
 
 def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, viewmat: torch.Tensor, campos: torch.Tensor,
                         K: torch.Tensor, width: int, height: int, radii: torch.Tensor, entry_grads: dict, *, sh_degree: int = 4,
-                        sh_layout: int = 1, eps2d: float = 0.3):
+                        sh_layout: int = 1, eps2d: float = 0.3, rasterize_mode: str = "classic",
+                        opacities: Optional[torch.Tensor] = None):
     """Backward of gs_project: the entry gradients of gs_rasterize_backward (or any dict with d_means2d, d_conics, d_colors,
     d_opacity) -> (d_means [U,3], d_covars [U,3,3], d_sh like sh, d_opacities [U]), summed over the cameras in index order.
-    Cameras are constants: there is no gradient for viewmat / campos / K."""
+    Cameras are constants: there is no gradient for viewmat / campos / K.  rasterize_mode="antialiased" needs `opacities` [U]:
+    d_opacity is then taken as the gradient of opacity * compensation, and the compensation's share reaches means and covars."""
+    mode = _gs_mode(rasterize_mode)
     Cn, U, sh_k = _gs_scene_args(means, covars, sh, viewmat, campos, K, sh_layout)
+    if mode:
+        if opacities is None:
+            raise ValueError("gs_project_backward: rasterize_mode='antialiased' needs opacities [U]")
+        _gs_f32(opacities, "opacities", U)
     if covars.numel() != 9 * U or sh.numel() != 3 * sh_k * U:
         raise ValueError("means / covars / sh disagree on the number of Gaussians")
     if radii.dtype != torch.int32 or not radii.is_contiguous() or radii.numel() != Cn * U:
@@ -1140,7 +1172,7 @@ def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Ten
     a = L.GsProjectBackwardArgs(_ptr(means), _ptr(covars), _ptr(sh), sh_layout, sh_k, sh_degree, _ptr(viewmat), _ptr(campos), _ptr(K), U, Cn,
                                 width, height, eps2d, _ptr(radii), _ptr(entry_grads["d_means2d"]), _ptr(entry_grads["d_conics"]),
                                 _ptr(entry_grads["d_colors"]), _ptr(entry_grads["d_opacity"]), _ptr(d_means), _ptr(d_covars), _ptr(d_sh),
-                                _ptr(d_op))
+                                _ptr(d_op), mode, _ptr(opacities) if mode else None)
     L.check(L.load().v3a_gs_project_backward(C.byref(a), _stream()), "v3a_gs_project_backward")
     return d_means, d_covars, d_sh, d_op
 
@@ -1148,48 +1180,54 @@ def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Ten
 class _GsRender(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, covars, sh, opacities, viewmat, campos, K, width, height, sh_degree, sh_layout, background, clamp_rgb,
-                workspace, n_isect_out):
-        pr = gs_project(means, covars, sh, viewmat, campos, K, width, height, sh_degree=sh_degree, sh_layout=sh_layout)
+                workspace, n_isect_out, rasterize_mode):
+        pr = gs_project(means, covars, sh, viewmat, campos, K, width, height, sh_degree=sh_degree, sh_layout=sh_layout,
+                        rasterize_mode=rasterize_mode)
         r = gs_rasterize(pr, opacities, width, height, background=background, clamp_rgb=clamp_rgb, workspace=workspace, return_order=True)
         if n_isect_out is not None:
             n_isect_out.append(r["n_isect"])
         ctx.save_for_backward(means, covars, sh, opacities, viewmat, campos, K, pr["radii"], pr["means2d"], pr["conics"], pr["colors"],
-                              r["tile_offsets"], r["flatten_ids"].contiguous())
-        ctx.cfg = (width, height, sh_degree, sh_layout, background, clamp_rgb, workspace)
+                              r["tile_offsets"], r["flatten_ids"].contiguous(), *([pr["compensations"]] if "compensations" in pr else []))
+        ctx.cfg = (width, height, sh_degree, sh_layout, background, clamp_rgb, workspace, rasterize_mode)
         return r["color"], r["depth"], r["alpha"]
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_color, d_depth, d_alpha):
-        means, covars, sh, opacities, viewmat, campos, K, radii, means2d, conics, colors, offs, ids = ctx.saved_tensors
-        width, height, sh_degree, sh_layout, background, clamp_rgb, workspace = ctx.cfg
+        means, covars, sh, opacities, viewmat, campos, K, radii, means2d, conics, colors, offs, ids, *comp = ctx.saved_tensors
+        width, height, sh_degree, sh_layout, background, clamp_rgb, workspace, rasterize_mode = ctx.cfg
         Cn = radii.shape[0]
         z = lambda g, *s: torch.zeros(Cn, height, width, *s, device=means.device, dtype=f32) if g is None else g.float().contiguous()
         if workspace is not None and workspace.bwd is None:
             workspace.bwd = GsBwdWorkspace()
         pr = dict(radii=radii, means2d=means2d, conics=conics, colors=colors)
+        if comp:
+            pr["compensations"] = comp[0]
         eg = gs_rasterize_backward(pr, opacities, width, height, offs, ids, z(d_color, 3), z(d_depth), z(d_alpha), background=background,
                                    clamp_rgb=clamp_rgb, workspace=workspace.bwd if workspace is not None else None)
         d_means, d_covars, d_sh, d_op = gs_project_backward(means, covars, sh, viewmat, campos, K, width, height, radii, eg,
-                                                            sh_degree=sh_degree, sh_layout=sh_layout)
-        return (d_means, d_covars, d_sh, d_op) + (None,) * 11
+                                                            sh_degree=sh_degree, sh_layout=sh_layout, rasterize_mode=rasterize_mode,
+                                                            opacities=opacities if comp else None)
+        return (d_means, d_covars, d_sh, d_op) + (None,) * 12
 
 
 def gs_render(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, opacities: torch.Tensor, viewmat: torch.Tensor,
               campos: torch.Tensor, K: torch.Tensor, width: int, height: int, *, sh_degree: int = 4, sh_layout: int = 1,
               background: Optional[torch.Tensor] = None, clamp_rgb: bool = True, workspace: Optional[GsWorkspace] = None,
-              n_isect_out: Optional[list] = None):
+              n_isect_out: Optional[list] = None, rasterize_mode: str = "classic"):
     """Differentiable gs_project + gs_rasterize for C cameras (viewmat [C,4,4], campos [C,3], K [C,3,3]) ->
     (color [C,H,W,3], depth [C,H,W], alpha [C,H,W]) with gradients to means, covars, sh and opacities through the HIP backward
     kernels (csrc/raster_bwd.hip).  The forward values are gs_rasterize's, bit for bit.  Cameras are constants (gsplat's optional
-    pose gradients are not implemented): viewmat / campos / K that require grad are refused.  First-order only."""
+    pose gradients are not implemented): viewmat / campos / K that require grad are refused.  First-order only.
+    rasterize_mode="antialiased": gsplat's mode of that name, forward and backward (every entry's opacity times its compensation)."""
+    _gs_mode(rasterize_mode)
     for t, n in ((viewmat, "viewmat"), (campos, "campos"), (K, "K")):
         if t.requires_grad:
             raise NotImplementedError(f"gs_render: no gradient for {n} (camera pose / intrinsics gradients are not implemented)")
     if viewmat.dim() != 3:
         raise ValueError("gs_render: viewmat [C,4,4], campos [C,3], K [C,3,3] required")
     return _GsRender.apply(means, covars, sh, opacities, viewmat, campos, K, width, height, sh_degree, sh_layout, background,
-                           clamp_rgb, workspace, n_isect_out)
+                           clamp_rgb, workspace, n_isect_out, rasterize_mode)
 
 
 def image_metrics(a_u8: torch.Tensor, b_u8: torch.Tensor):
@@ -1674,6 +1712,41 @@ def splat_activate(log_scales: torch.Tensor, quats: torch.Tensor, logits: torch.
     _f32_dev(quats, "quats", (U, 4))
     _f32_dev(logits, "logits", (U,))
     return _SplatActivate.apply(log_scales, quats, logits)
+
+
+class _SplatRegularisers(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, log_scales, logits):
+        U = logits.shape[0]
+        lib = L.load()
+        ws, ws_bytes = _workspace(lib.v3a_splat_reg_workspace_bytes(U), f"v3a_splat_reg_workspace_bytes (U = {U})", logits.device)
+        out = torch.empty(2, device=logits.device, dtype=torch.float64)
+        L.check(lib.v3a_splat_reg(_ptr(logits), _ptr(log_scales), U, _ptr(out), _ptr(ws), ws_bytes, _stream()), "v3a_splat_reg")
+        ctx.save_for_backward(log_scales, logits)
+        return out[0], out[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_opacity, d_scale):
+        log_scales, logits = ctx.saved_tensors
+        z = torch.zeros((), device=logits.device, dtype=torch.float64)
+        d_out = torch.stack([z if g is None else g.to(torch.float64).reshape(()) for g in (d_opacity, d_scale)])
+        d_ls, d_lg = torch.empty_like(log_scales), torch.empty_like(logits)
+        L.check(L.load().v3a_splat_reg_backward(_ptr(logits), _ptr(log_scales), logits.shape[0], _ptr(d_out), _ptr(d_lg), _ptr(d_ls),
+                                                _stream()), "v3a_splat_reg_backward")
+        return d_ls, d_lg
+
+
+def splat_regularisers(log_scales: torch.Tensor, logits: torch.Tensor):
+    """The reference loop's two regularisers (simple_trainer.py:966-977; csrc/splat_reg.hip) of log-scales [U,3] and opacity logits
+    [U] -> (opacity_mean, scale_mean) = (sigmoid(logits).mean(), exp(log_scales).mean()): float64 scalars on the device, summed in
+    fp64 in a fixed order (bit-identical run to run), differentiable with respect to both inputs (HIP backward, first order only)."""
+    U = logits.shape[0]
+    if U < 1:
+        raise ValueError("splat_regularisers: no Gaussians")
+    _f32_dev(log_scales, "log_scales", (U, 3))
+    _f32_dev(logits, "logits", (U,))
+    return _SplatRegularisers.apply(log_scales, logits)
 
 
 def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, *, lr: float, step: int, betas=(0.9, 0.999),

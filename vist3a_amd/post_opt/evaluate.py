@@ -25,9 +25,10 @@ from .trainer import _cameras, _single
 
 
 def evaluate_views(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.Tensor, intrinsics: torch.Tensor, *,
-                   color_correct: bool = False, lpips=None) -> dict:
+                   color_correct: bool = False, lpips=None, antialiased: bool = False) -> dict:
     """`images` f32 [V,H,W,3] in [0,1] on the device, `extrinsics` camera-to-world [V,4,4], `intrinsics` normalised [V,3,3], as
-    post_optimize takes them (H, W >= 11 for the SSIM window).  Nothing here has a gradient."""
+    post_optimize takes them (H, W >= 11 for the SSIM window).  `antialiased`: render in the rasteriser's antialiased mode, as a
+    scene fitted with PostOptConfig.antialiased wants to be seen.  Nothing here has a gradient."""
     _single(gaussians)
     if images.dim() != 4 or images.shape[-1] != 3 or images.dtype != torch.float32:
         raise ValueError(f"images must be float32 [V,H,W,3], got {images.dtype} {tuple(images.shape)}")
@@ -53,7 +54,8 @@ def evaluate_views(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch
             torch.cuda.synchronize(dev)
             tic = time.perf_counter()
             color, _, _ = ops.gs_render(means, cov, sh, op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H, sh_degree=sh_degree,
-                                        sh_layout=1, background=background, clamp_rgb=True, workspace=ws)
+                                        sh_layout=1, background=background, clamp_rgb=True, workspace=ws,
+                                        rasterize_mode="antialiased" if antialiased else "classic")
             torch.cuda.synchronize(dev)
             seconds += time.perf_counter() - tic
             renders.append(color.clamp(0, 1))

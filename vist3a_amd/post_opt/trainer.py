@@ -15,6 +15,11 @@ lib_bilagrid.py): the render goes through ops.bilagrid_slice with the view's gri
 cfg.bilagrid_tv_lambda * ops.bilagrid_tv(all grids), and the grids [V,L,GY,GX,12] train with an Adam and a warm-up schedule of their
 own.  They absorb per-view exposure and white balance so that the scene does not; they stay in `splats` and are not exported.
 
+Four more switches of the reference's Config, all off by default: cfg.antialiased (:323-324, :769-770) renders every step in the
+rasteriser's antialiased mode; cfg.random_bkgd (:326-327, :925-927) draws a fresh RGB background per step; cfg.opacity_reg and
+cfg.scale_reg (:329-332, :966-977) add weight * mean sigmoid(logit) and weight * mean exp(log-scale), both from
+ops.splat_regularisers (one HIP reduction), only when the weight is above 0.
+
 The harmonics stay ONE [U,3,K] tensor: the reference's sh0 / shN optimisers (rates lr_sh and lr_sh / 20) are one ops.adam_step with
 a period of K, which is the same arithmetic because Adam is elementwise."""
 from __future__ import annotations
@@ -52,6 +57,10 @@ class PostOptConfig:
     bilagrid_lr: float = 2e-3        # :707, times sqrt(batch_size) = 1
     bilagrid_warmup_steps: int = 1000   # :839: LinearLR(0.01 -> 1) chained with the decay to 1 % over max_steps
     bilagrid_tv_lambda: float = 10.0    # :963
+    antialiased: bool = False        # :323-324: rasterize_mode="antialiased" (the loop's renders; evaluation and export follow it)
+    random_bkgd: bool = False        # :326-327: a random background per step, to discourage transparency
+    opacity_reg: float = 0.0         # :329-330: weight of mean sigmoid(logit), added when > 0
+    scale_reg: float = 0.0           # :331-332: weight of mean exp(log-scale), added when > 0
     test_every: int = 0              # k > 0: the views with index % k == 0 are held out of the loop (the reference's dataset split, test_every)
     # ours
     params: Tuple[str, ...] = ("means", "scales", "quats", "opacities", "sh0", "shN")
@@ -95,6 +104,27 @@ def view_order(n_views: int, steps: int, seed: int) -> list:
     while len(out) < steps:
         out += torch.randperm(n_views, generator=g).tolist()
     return out[:steps]
+
+
+def random_backgrounds(steps: int, seed: int) -> torch.Tensor:
+    """cfg.random_bkgd's background of every step, f32 [steps,3] in [0,1): one torch.rand(3) per step from a CPU generator seeded
+    `seed` + 1, a generator of its own so that switching the option on leaves view_order where it was."""
+    g = torch.Generator().manual_seed(int(seed) + 1)
+    return torch.stack([torch.rand(3, generator=g) for _ in range(steps)]) if steps > 0 else torch.zeros(0, 3)
+
+
+def log_columns(cfg: "PostOptConfig") -> list:
+    """The names of post_optimize's log columns for `cfg`, in order."""
+    cols = ["loss", "l1", "ssim"]
+    if cfg.depth_loss:
+        cols.append("depth_term")
+    if cfg.use_bilateral_grid:
+        cols.append("bilagrid_tv")
+    if cfg.opacity_reg > 0.0:
+        cols.append("opacity_mean")
+    if cfg.scale_reg > 0.0:
+        cols.append("scale_mean")
+    return cols
 
 
 def train_views(n_views: int, test_every: int) -> list:
@@ -188,7 +218,13 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     `depth_masks` bool / uint8 [V,H,W] (or None: every pixel with a positive finite depth).  Without cfg.depth_loss `depths` is ignored.
 
     With cfg.test_every = k > 0 the views with index % k == 0 are never shown (train_view_order); their images and depths
-    are not read, and there is one bilateral grid per TRAINING view, in their order.  post_opt.evaluate_views scores them."""
+    are not read, and there is one bilateral grid per TRAINING view, in their order.  post_opt.evaluate_views scores them.
+
+    cfg.antialiased renders in the rasteriser's antialiased mode.  cfg.random_bkgd replaces the black background of step i by
+    random_backgrounds(steps, cfg.seed)[i]; the target image is not composited over it (as in the reference), and the render is
+    clamped to [0,1] AFTER the background went in (the reference adds it to an unclamped render: a deviation).  cfg.opacity_reg /
+    cfg.scale_reg > 0 add weight * ops.splat_regularisers(...) terms to the loss and, each, one last log column with the unweighted
+    mean, opacity before scale, after every other column (log_columns(cfg) names them all)."""
     cfg = cfg or PostOptConfig()
     cfg.check_bilagrid()
     _single(gaussians)
@@ -235,7 +271,10 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     view, campos, Kpix = _cameras(extrinsics, intrinsics, W, H, dev)
     images = images.contiguous()
     background = torch.zeros(3, device=dev, dtype=torch.float32)
-    log = torch.zeros(steps, 3 + int(cfg.depth_loss) + int(bil), device=dev, dtype=torch.float64)
+    bkgds = random_backgrounds(steps, cfg.seed).to(dev) if cfg.random_bkgd else None
+    mode = "antialiased" if cfg.antialiased else "classic"
+    reg_op, reg_sc = cfg.opacity_reg > 0.0, cfg.scale_reg > 0.0
+    log = torch.zeros(steps, len(log_columns(cfg)), device=dev, dtype=torch.float64)
     lrs = dict(means=cfg.lr_means, scales=cfg.lr_scales, quats=cfg.lr_quats, opacities=cfg.lr_opacities, sh=cfg.lr_sh)
     decay = 0.01 ** (1.0 / cfg.max_steps)
     ws = ops.GsWorkspace()
@@ -246,7 +285,8 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
         for i, j in enumerate(train_view_order(V, steps, cfg.seed, cfg.test_every)):
             cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
             color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
-                                        sh_degree=sh_degree, sh_layout=1, background=background, clamp_rgb=True, workspace=ws)
+                                        sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
+                                        clamp_rgb=True, workspace=ws, rasterize_mode=mode)
             if bil:
                 color = ops.bilagrid_slice(color, splats["bil_grids"][grid_of[j]:grid_of[j] + 1])
             loss, l1, ssim = ops.photometric_loss(color, images[j:j + 1], cfg.ssim_lambda)
@@ -260,6 +300,15 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
                 tv = ops.bilagrid_tv(splats["bil_grids"])
                 loss = loss + cfg.bilagrid_tv_lambda * tv
                 rec = [loss.detach()] + rec[1:] + [tv.detach()]
+            if reg_op or reg_sc:
+                op_mean, sc_mean = ops.splat_regularisers(p["scales"], p["opacities"])
+                if reg_op:
+                    loss = loss + cfg.opacity_reg * op_mean
+                    rec.append(op_mean.detach())
+                if reg_sc:
+                    loss = loss + cfg.scale_reg * sc_mean
+                    rec.append(sc_mean.detach())
+                rec[0] = loss.detach()
             grads = torch.autograd.grad(loss, leaves)
             log[i].copy_(torch.stack(rec))
             t = splats["step"] + 1

@@ -50,6 +50,16 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
     g.add_argument("--post_opt_bilateral_grid", action="store_true",
                    help="post-optimisation with one bilateral grid per view (the reference's use_bilateral_grid): the grids absorb the "
                         "frames' exposure and white-balance drift instead of the scene; they are not exported")
+    g.add_argument("--post_opt_antialiased", action="store_true",
+                   help="post-optimisation in the rasteriser's antialiased mode (the reference's antialiased; gsplat "
+                        "rasterize_mode=\"antialiased\"): a Gaussian thinner than a pixel is dimmed as well as widened, so the scene "
+                        "holds up at other resolutions; the evaluation and the videos then render in that mode too")
+    g.add_argument("--post_opt_random_bkgd", action="store_true",
+                   help="post-optimisation against a random background per step (the reference's random_bkgd), to discourage transparency")
+    g.add_argument("--post_opt_opacity_reg", type=float, default=0.0, metavar="X",
+                   help="weight of the mean opacity in the post-optimisation loss (the reference's opacity_reg); 0 = off")
+    g.add_argument("--post_opt_scale_reg", type=float, default=0.0, metavar="X",
+                   help="weight of the mean scale in the post-optimisation loss (the reference's scale_reg); 0 = off")
     g.add_argument("--post_opt_eval_every", type=int, default=0, metavar="K",
                    help="hold the views with index %% K == 0 out of the post-optimisation (the reference's test_every) and evaluate them "
                         "before and after it: PSNR, SSIM, the number of Gaussians and a time per image - with --post_opt_bilateral_grid "
