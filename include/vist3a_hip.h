@@ -38,7 +38,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 30) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 31) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -795,6 +795,68 @@ long v3a_splat_reg_workspace_bytes(long U);   /* V3A_ERR_SHAPE for U < 1 or 3 U 
 int v3a_splat_reg(const float* logits, const float* log_scales, long U, double* out, void* workspace, long workspace_bytes, void* stream);
 int v3a_splat_reg_backward(const float* logits, const float* log_scales, long U, const double* d_out, float* d_logits,
                            float* d_log_scales, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The MCMC strategy of the post-optimisation loop (csrc/mcmc.hip; gsplat's MCMCStrategy, which simple_trainer.py:1142-1150 calls
+ * in its `mcmc` configuration).  DESIGN.md section 7f restates the algorithm and is the contract.
+ *
+ * Random numbers: Philox4x32-10, counter (slot, 0, rng_stream, step), key = seed (low word, high word); no state.  rng_stream 0 is
+ * relocation sampling, 1 growth sampling, 2 and 3 the two normal draws of the noise.  A uniform of words (x0, x1) is
+ * ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 in [0, 1).  v3a_mcmc_philox and v3a_mcmc_uniform run on the HOST (host pointers): the same
+ * source as the device code, for known-answer tests.
+ * ---------------------------------------------------------------------------------------------- */
+int v3a_mcmc_philox(const uint32_t* counter /* [4] */, const uint32_t* key /* [2] */, uint32_t* out /* [4] */);
+double v3a_mcmc_uniform(uint32_t x0, uint32_t x1);
+
+/* Weighted sampler.  weights f32 [U] (opacities); src int32 [n_slots]; counts int32 [U], zeroed by the call, then counts[src[s]] += 1
+ * for every slot that drew (integer atomics: they commute).
+ *   alive_only = 1 (relocation): n_slots == U; slot s is active iff weights[s] <= min_weight, inactive slots get src = -1; the pool is
+ *                                weights[i] where above min_weight, else 0.
+ *   alive_only = 0 (growth):     every slot is active, the pool is all weights; min_weight is ignored.
+ * All sums in fp64 on the exactly converted weights: blocks of 1024 consecutive Gaussians, block total T_b = each of 256 lanes adds
+ * its 4 consecutive elements in index order, then block_sum<256> of csrc/fixed_sum.h; P_b = the exclusive prefix of T_b added
+ * sequentially in block order, total = P_last + T_last.  An active slot draws t = u total, takes b = the last block with T_b > 0 and
+ * P_b <= t, walks it in index order (c = P_b; c += w_i) and picks the first i with w_i > 0 and c > t, or else the block's last i
+ * with w_i > 0.  total == 0 or no active slot: every src is -1, every count 0, no error.  Nothing is read back to the host.
+ * workspace: v3a_mcmc_sample_workspace_bytes(U), 8-byte aligned (too small or misaligned: -4). */
+long v3a_mcmc_sample_workspace_bytes(long U);   /* V3A_ERR_SHAPE for U < 1 or U > 2^31 - 1 */
+int v3a_mcmc_sample(const float* weights, long U, float min_weight, int alive_only, long n_slots, unsigned long long seed,
+                    unsigned int rng_stream, unsigned int step, int* src, int* counts, void* workspace, long workspace_bytes, void* stream);
+
+/* Relocation (dst_offset == 0, n_slots == U: slot s is row s, a dead row) and growth (dst_offset == U: slot s is row U + s of
+ * tensors the caller allocated with U + n_slots rows and filled up to U), from the sampler's src and counts.  For a source j
+ * (counts[j] > 0), in fp64 with one rounding per f32 store:
+ *   r = min(counts[j] + 1, 51), op = sigmoid(logit_j), o' = 1 - (1 - op)^(1/r),
+ *   den = sum_{i=1..r} sum_{k=0..i-1} C(i-1, k) (-1)^k / sqrt(k+1) o'^(k+1),  scale' = (op / den) exp(log_scale_j),
+ *   stored: logit(clamp(o', min_opacity, 1 - 2^-23)) and log(scale').
+ * Row j takes the new logit and log-scales; the row of every slot with src == j takes them too, with means, quats and sh of row j.
+ * Moments: relocation zeroes m and v of row j in all five tensors and leaves the dead row's; growth zeroes the new row's and leaves
+ * row j's.  Per-source values go to the workspace first, then every row is written by exactly one thread: the result does not
+ * depend on execution order.  Rows that are neither source nor destination are not touched.  src and counts must be one
+ * v3a_mcmc_sample's output (a slot whose src is out of range or has counts 0 is skipped).
+ * workspace: v3a_mcmc_relocate_workspace_bytes(U) (16 U), 8-byte aligned. */
+typedef struct {
+  const int* src;      /* [n_slots] */
+  const int* counts;   /* [U] */
+  float *means, *log_scales, *quats, *logits, *sh;            /* [rows,3] [rows,3] [rows,4] [rows] [rows,3,K]; rows = U or U + n_slots */
+  float *m_means, *m_log_scales, *m_quats, *m_logits, *m_sh;  /* Adam's first moments, same shapes */
+  float *v_means, *v_log_scales, *v_quats, *v_logits, *v_sh;  /* Adam's second moments */
+  long U, n_slots, dst_offset;
+  int K;
+  double min_opacity;                         /* in (0, 1) */
+  void* workspace; long workspace_bytes;
+} v3a_mcmc_relocate_args;
+long v3a_mcmc_relocate_workspace_bytes(long U);   /* V3A_ERR_SHAPE for U < 1 or U > 2^31 - 1 */
+int v3a_mcmc_relocate(const v3a_mcmc_relocate_args* a, void* stream);
+
+/* The per-step noise, in place on means f32 [U,3], one thread per Gaussian, fp64 after the loads, one rounding at the store:
+ *   op = sigmoid(logit), gate = 1 / (1 + exp(-100 ((1 - op) - 0.995))), cov = R diag(exp(2 log_scale)) R^T with R from the raw
+ *   quaternion by v3a_splat_activate's expression (evaluated in fp64), xi = (z0, z1) of rng_stream 2 and z0 of rng_stream 3 at
+ *   slot i (Box-Muller: r = sqrt(-2 ln(1 - u1)), z0 = r cos(2 pi u2), z1 = r sin(2 pi u2), u1 from words 0-1, u2 from words 2-3),
+ *   means_i += cov (xi gate scaler).
+ * 44 bytes read and 12 written per Gaussian; the quaternion is one 16-byte load when its pointer is 16-byte aligned. */
+int v3a_mcmc_noise(float* means, const float* log_scales, const float* quats, const float* logits, long U, double scaler,
+                   unsigned long long seed, unsigned int step, void* stream);
 
 #ifdef __cplusplus
 }

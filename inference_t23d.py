@@ -65,11 +65,12 @@ def build_text_encoder(args, device):
 
 
 def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False, eval_every=0, lpips=None,
-           antialiased=False, random_bkgd=False, opacity_reg=0.0, scale_reg=0.0):
+           antialiased=False, random_bkgd=False, opacity_reg=0.0, scale_reg=0.0, mcmc=None):
     """-> (refined Gaussians, stats or None).  With eval_every = K > 0 the views with index % K == 0 are held out of the loop and
     scored before and after it: stats = {"before": {...}, "after": {...}, "held_out": [...]} (vist3a_amd.post_opt.evaluate_views).
     antialiased / random_bkgd / opacity_reg / scale_reg: the PostOptConfig fields of those names; the evaluation renders in the
-    loop's rasterize mode."""
+    loop's rasterize mode.  mcmc: None, or (cap_max, (start, stop, every)) to run the loop with cfg.strategy = "mcmc"; the refined
+    scene then has as many Gaussians as the strategy left it with."""
     from vist3a_amd import ops
     from vist3a_amd.post_opt import PostOptConfig, evaluate_views, post_optimize, train_views
     with torch.no_grad():
@@ -90,6 +91,9 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
     cfg.test_every = int(eval_every)
     cfg.antialiased, cfg.random_bkgd = bool(antialiased), bool(random_bkgd)
     cfg.opacity_reg, cfg.scale_reg = float(opacity_reg), float(scale_reg)
+    if mcmc is not None:
+        cfg.strategy, cfg.mcmc_cap_max = "mcmc", int(mcmc[0])
+        cfg.mcmc_refine_start_iter, cfg.mcmc_refine_stop_iter, cfg.mcmc_refine_every = (int(x) for x in mcmc[1])
     ext, intr = pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach()
     stats = None
     if cfg.test_every > 0:
@@ -102,6 +106,23 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
     if stats is not None:
         stats = dict(before=stats["before"], after=score(g), held_out=stats["held_out"])
     return g, stats
+
+
+def mcmc_options(args):
+    """--post_opt_mcmc* -> None (off) or (cap_max, (start, stop, every)) for refine()"""
+    if not args.post_opt_mcmc:
+        return None
+    if args.post_opt_steps <= 0:
+        raise ValueError("--post_opt_mcmc needs --post_opt_steps > 0 (it is a strategy of the post-optimisation)")
+    try:
+        refine_at = tuple(int(x) for x in args.post_opt_mcmc_refine.split(","))
+    except ValueError:
+        refine_at = ()
+    if len(refine_at) != 3 or refine_at[2] < 1:
+        raise ValueError(f"--post_opt_mcmc_refine wants three integers START,STOP,EVERY with EVERY >= 1, got {args.post_opt_mcmc_refine!r}")
+    if args.post_opt_mcmc_cap_max < 1:
+        raise ValueError("--post_opt_mcmc_cap_max must be positive")
+    return args.post_opt_mcmc_cap_max, refine_at
 
 
 def main(args):
@@ -128,6 +149,7 @@ def main(args):
         raise ValueError("--post_opt_eval_every K needs K >= 0 and --post_opt_steps > 0 (it evaluates the views held out of the refinement)")
     if args.post_opt_opacity_reg < 0 or args.post_opt_scale_reg < 0:
         raise ValueError("--post_opt_opacity_reg and --post_opt_scale_reg are weights >= 0")
+    mcmc = mcmc_options(args)
     if (args.lpips_vgg_weights is None) != (args.lpips_lin_weights is None):
         raise ValueError("--lpips_vgg_weights and --lpips_lin_weights go together: give both or neither")
     lpips = None
@@ -157,7 +179,7 @@ def main(args):
             g, stats = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps, out.depth_dict,
                               args.post_opt_depth_lambda, args.post_opt_bilateral_grid, args.post_opt_eval_every, lpips,
                               antialiased=args.post_opt_antialiased, random_bkgd=args.post_opt_random_bkgd,
-                              opacity_reg=args.post_opt_opacity_reg, scale_reg=args.post_opt_scale_reg)
+                              opacity_reg=args.post_opt_opacity_reg, scale_reg=args.post_opt_scale_reg, mcmc=mcmc)
             if stats is not None:
                 (save / "post_opt_stats.json").write_text(json.dumps(stats, indent=1))
         if not args.no_video:  # orbit video through the predicted context poses (reference :144-154)

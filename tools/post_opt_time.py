@@ -7,7 +7,11 @@ total-variation launches are timed as a part of their own ("bilagrid": both forw
 grid's Adam into "adam").
 A second JSON line times the evaluation-time colour fit on one image pair of the same size (csrc/color_correct.hip, 5 rounds = 12
 launches) next to the plain MSE (ops.image_mse, 2 launches): milliseconds, and the fit's bytes read per round (img + one channel
-of ref per workgroup row, 3 x 16 B per pixel) over its time.  It runs outside the step: the loop never calls it."""
+of ref per workgroup row, 3 x 16 B per pixel) over its time.  It runs outside the step: the loop never calls it.
+With --mcmc a third JSON line times the MCMC strategy (csrc/mcmc.hip) on the same Gaussians: the per-step noise (ops.mcmc_noise, 44 B
+read and 12 B written per Gaussian) against a `copy_` of the same 56 B per Gaussian, and one refine's pieces - the relocation sampler and
+relocation with 10 % of the scene dead, the growth sampler for 5 % more rows and the growth itself (the reallocation of the fifteen
+tensors is the caller's torch work and is not timed)."""
 import argparse
 import json
 import math
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--antialiased", action="store_true", help="the loop's renders in the rasteriser's antialiased mode")
     ap.add_argument("--bilateral_grid", action="store_true")
+    ap.add_argument("--mcmc", action="store_true", help="also time the MCMC strategy's noise launch and the pieces of one refine")
     a = ap.parse_args()
     from vist3a_amd import ops
     U, W, H = a.gaussians, a.size, a.size
@@ -113,6 +118,49 @@ def main():
     f_ms, m_ms = statistics.median(tf), statistics.median(tm)
     print(json.dumps(dict(size=W, color_correct_iters=5, color_correct_ms=round(f_ms, 3), color_correct_ms_per_round=round(f_ms / 5, 3),
                           color_correct_read_GBps=round(5 * 48 * W * H / f_ms / 1e6, 1), image_mse_ms=round(m_ms, 3))))
+    if a.mcmc:
+        print(json.dumps(mcmc_times(ops, {k: t.detach() for k, t in p.items()}, m, v, a.warmup, a.iters)))
+
+
+def mcmc_times(ops, p, m, v, warmup, iters):
+    U = p["means"].shape[0]
+    timed = {}
+
+    def clock(name, fn, setup=None):
+        ms = []
+        for it in range(warmup + iters):
+            state = setup() if setup is not None else None
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(it, state)
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                ms.append(e0.elapsed_time(e1))
+        timed[name] = statistics.median(ms)
+        return out
+
+    with torch.no_grad():
+        logits = p["opacities"].clone()
+        logits[::10] = -7.0                                    # 10 % of the scene dead (opacity 0.0009), and with an open noise gate
+        means = p["means"].clone()
+        clock("noise", lambda it, _: ops.mcmc_noise(means, p["scales"], p["quats"], logits, scaler=80.0, seed=1, step=it + 1))
+        src_b, dst_b = torch.empty(U * 7, device="cuda"), torch.empty(U * 7, device="cuda")      # 28 B read + 28 B written per Gaussian
+        clock("copy_same_bytes", lambda it, _: dst_b.copy_(src_b))
+        _, op = ops.splat_activate(p["scales"], p["quats"], logits)
+        src, counts = clock("relocate_sample", lambda it, _: ops.mcmc_sample(op, min_weight=0.005, alive_only=True, n_slots=U, seed=1, stream=0, step=it + 1))
+        fresh = lambda: [dict(p, opacities=logits.clone(), scales=p["scales"].clone()), m, v]
+        clock("relocate", lambda it, st: ops.mcmc_relocate(src, counts, *st, dst_offset=0, min_opacity=0.005), setup=fresh)
+        n = U // 20
+        gsrc, gcounts = clock("grow_sample", lambda it, _: ops.mcmc_sample(op, min_weight=0.005, alive_only=False, n_slots=n, seed=1, stream=1, step=it + 1))
+        longer = lambda d: {k: torch.cat([t.detach(), torch.zeros((n,) + tuple(t.shape[1:]), device="cuda")]) for k, t in d.items()}
+        grown = [longer(dict(p, opacities=logits)), longer(m), longer(v)]
+        clock("grow", lambda it, _: ops.mcmc_relocate(gsrc, gcounts, *grown, dst_offset=U, min_opacity=0.005))
+    nbytes = U * 56
+    return dict(gaussians=U, mcmc_noise_ms=round(timed["noise"], 4), mcmc_noise_GBps=round(nbytes / timed["noise"] / 1e6, 1),
+                noise_bytes=nbytes, copy_same_bytes_ms=round(timed["copy_same_bytes"], 4),
+                noise_over_copy=round(timed["noise"] / timed["copy_same_bytes"], 2), dead=int(U // 10 + (U % 10 > 0)), added=n,
+                **{k + "_ms": round(timed[k], 4) for k in ("relocate_sample", "relocate", "grow_sample", "grow")})
 
 
 if __name__ == "__main__":

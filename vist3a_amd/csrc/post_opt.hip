@@ -8,24 +8,10 @@
 //   fused Adam         torch.optim.Adam's update on one parameter tensor per launch (simple_trainer.py:442-460: one optimiser per
 //                      tensor, eps 1e-15), in place.
 #include "common.h"
+#include "splat_quat.h"   // quat_R: the rotation of a raw quaternion, shared with mcmc.hip
 #include "../../include/vist3a_hip.h"
 
 namespace {
-
-// rotation of a quaternion (i, j, k, r), normalised the way the adapter normalises it
-__device__ __forceinline__ void quat_R(const float* qin, float* R) {
-  float q[4], n2 = 0.f;
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { q[e] = qin[e]; n2 += q[e] * q[e]; }
-  const float inv = 1.f / (sqrtf(n2) + 1e-8f);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) q[e] *= inv;
-  const float i = q[0], j = q[1], k = q[2], r = q[3];
-  const float two_s = 2.0f / (i * i + j * j + k * k + r * r);
-  R[0] = 1 - two_s * (j * j + k * k); R[1] = two_s * (i * j - k * r);     R[2] = two_s * (i * k + j * r);
-  R[3] = two_s * (i * j + k * r);     R[4] = 1 - two_s * (i * i + k * k); R[5] = two_s * (j * k - i * r);
-  R[6] = two_s * (i * k - j * r);     R[7] = two_s * (j * k + i * r);     R[8] = 1 - two_s * (i * i + j * j);
-}
 
 // One thread per Gaussian: 8 floats in, 10 out; rows of adjacent lanes are adjacent in memory.
 __global__ void __launch_bounds__(256) splat_activate_kernel(const float* __restrict__ log_scales, const float* __restrict__ quats,

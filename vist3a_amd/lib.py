@@ -305,6 +305,19 @@ class AdamArgs(C.Structure):
     ]
 
 
+class McmcRelocateArgs(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("counts", C.c_void_p),
+        ("means", C.c_void_p), ("log_scales", C.c_void_p), ("quats", C.c_void_p), ("logits", C.c_void_p), ("sh", C.c_void_p),
+        ("m_means", C.c_void_p), ("m_log_scales", C.c_void_p), ("m_quats", C.c_void_p), ("m_logits", C.c_void_p), ("m_sh", C.c_void_p),
+        ("v_means", C.c_void_p), ("v_log_scales", C.c_void_p), ("v_quats", C.c_void_p), ("v_logits", C.c_void_p), ("v_sh", C.c_void_p),
+        ("U", C.c_long), ("n_slots", C.c_long), ("dst_offset", C.c_long),
+        ("K", C.c_int),
+        ("min_opacity", C.c_double),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
 # name -> (restype, argtypes); every symbol include/vist3a_hip.h declares must be listed here
 SYMBOLS = {
     "v3a_abi_version": (C.c_int, []),
@@ -394,10 +407,18 @@ SYMBOLS = {
     "v3a_splat_reg_workspace_bytes": (C.c_long, [C.c_long]),
     "v3a_splat_reg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
     "v3a_splat_reg_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 4),
+    "v3a_mcmc_philox": (C.c_int, [C.POINTER(C.c_uint32)] * 3),
+    "v3a_mcmc_uniform": (C.c_double, [C.c_uint32, C.c_uint32]),
+    "v3a_mcmc_sample_workspace_bytes": (C.c_long, [C.c_long]),
+    "v3a_mcmc_sample": (C.c_int, [C.c_void_p, C.c_long, C.c_float, C.c_int, C.c_long, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_long, C.c_void_p]),
+    "v3a_mcmc_relocate_workspace_bytes": (C.c_long, [C.c_long]),
+    "v3a_mcmc_relocate": (C.c_int, [C.POINTER(McmcRelocateArgs), C.c_void_p]),
+    "v3a_mcmc_noise": (C.c_int, [C.c_void_p] * 4 + [C.c_long, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 30   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 31   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

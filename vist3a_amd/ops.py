@@ -1762,3 +1762,89 @@ def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor
     a = L.AdamArgs(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(lr if lr2 is None else lr2), int(period), b1, b2, float(eps),
                    1.0 - b1 ** step, 1.0 - b2 ** step)
     L.check(L.load().v3a_adam_step(C.byref(a), _stream()), "v3a_adam_step")
+
+
+MCMC_STREAMS = dict(relocate=0, grow=1)   # the sampler's random streams (2 and 3 are the noise's draws)
+
+
+def _mcmc_key(seed: int, step: int, what: str):
+    seed, step = int(seed), int(step)
+    if not 0 <= seed < 2 ** 64 or not 0 <= step < 2 ** 32:
+        raise ValueError(f"{what}: seed must fit 64 bits and step 32 bits, both unsigned, got {seed} and {step}")
+    return seed, step
+
+
+def mcmc_sample(weights: torch.Tensor, *, min_weight: float, alive_only: bool, n_slots: int, seed: int, stream: int, step: int):
+    """The MCMC strategy's weighted sampler (csrc/mcmc.hip, v3a_mcmc_sample) over opacities `weights` f32 [U] -> (src int32 [n_slots],
+    counts int32 [U]).  alive_only (relocation, n_slots == U): slot s draws iff weights[s] <= min_weight, among the Gaussians above
+    it; otherwise (growth) every slot draws among all.  src is the drawn row or -1, counts how often each row was drawn.  Philox
+    counter (slot, 0, stream, step) under the key `seed`; fp64 sums in a fixed order: bit-identical run to run and reproducible on
+    the host (tests/mcmc_oracle.py).  An empty pool, or no slot that draws, is a no-op (all -1, all 0)."""
+    U = weights.shape[0] if weights.dim() == 1 else 0
+    if U < 1:
+        raise ValueError("mcmc_sample: no Gaussians")
+    _f32_dev(weights, "weights", (U,))
+    n_slots = int(n_slots)
+    if n_slots < 1 or (alive_only and n_slots != U):
+        raise ValueError(f"mcmc_sample: n_slots must be positive, and U = {U} with alive_only, got {n_slots}")
+    if stream not in (0, 1):
+        raise ValueError(f"mcmc_sample: stream is 0 (relocation) or 1 (growth), got {stream!r}")
+    seed, step = _mcmc_key(seed, step, "mcmc_sample")
+    lib = L.load()
+    ws, ws_bytes = _workspace(lib.v3a_mcmc_sample_workspace_bytes(U), f"v3a_mcmc_sample_workspace_bytes (U = {U})", weights.device)
+    src = torch.empty(n_slots, device=weights.device, dtype=torch.int32)
+    counts = torch.empty(U, device=weights.device, dtype=torch.int32)
+    L.check(lib.v3a_mcmc_sample(_ptr(weights), U, float(min_weight), int(bool(alive_only)), n_slots, seed, int(stream), step, _ptr(src),
+                                _ptr(counts), _ptr(ws), ws_bytes, _stream()), "v3a_mcmc_sample")
+    return src, counts
+
+
+_MCMC_TENSORS = ("means", "scales", "quats", "opacities", "sh")
+
+
+def mcmc_relocate(src: torch.Tensor, counts: torch.Tensor, params: dict, m: dict, v: dict, *, dst_offset: int, min_opacity: float) -> None:
+    """Relocation (dst_offset = 0) or growth (dst_offset = U) from mcmc_sample's (src, counts), in place on `params` and Adam's
+    moments `m`, `v`: dicts of means [R,3], scales (logs) [R,3], quats [R,4], opacities (logits) [R], sh [R,3,K], f32, with R = U
+    rows (relocation, src [U]) or R = U + n rows filled up to U (growth, src [n]).  Every drawn row j and its copies get
+    compute_relocation's opacity and scales for counts[j] + 1 copies (fp64, csrc/mcmc.hip); copies take means, quats and sh of j.
+    Relocation zeroes the moments of j and leaves the dead row's; growth zeroes the new row's and leaves j's."""
+    U, n = counts.shape[0], src.shape[0]
+    dst_offset = int(dst_offset)
+    if dst_offset not in (0, U) or (dst_offset == 0 and n != U):
+        raise ValueError(f"mcmc_relocate: dst_offset is 0 with src [U] (relocation) or U (growth), got {dst_offset} with U = {U}, src [{n}]")
+    rows = U if dst_offset == 0 else U + n
+    for name, t in (("src", src), ("counts", counts)):
+        if not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"mcmc_relocate: {name} must be a contiguous int32 device vector, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    sh = params["sh"]
+    if sh.dim() != 3 or sh.shape[1] != 3 or sh.shape[2] < 1:
+        raise ValueError(f"mcmc_relocate: sh must be [rows,3,K], got {tuple(sh.shape)}")
+    K = sh.shape[2]
+    shapes = dict(means=(rows, 3), scales=(rows, 3), quats=(rows, 4), opacities=(rows,), sh=(rows, 3, K))
+    for group, d in (("params", params), ("m", m), ("v", v)):
+        for name in _MCMC_TENSORS:
+            _f32_dev(d[name], f"{group}[{name!r}]", shapes[name])
+    if not 0.0 < float(min_opacity) < 1.0:
+        raise ValueError(f"mcmc_relocate: min_opacity must lie in (0, 1), got {min_opacity!r}")
+    lib = L.load()
+    ws, ws_bytes = _workspace(lib.v3a_mcmc_relocate_workspace_bytes(U), f"v3a_mcmc_relocate_workspace_bytes (U = {U})", src.device)
+    a = L.McmcRelocateArgs(_ptr(src), _ptr(counts), *(_ptr(d[name]) for d in (params, m, v) for name in _MCMC_TENSORS), U, n, dst_offset, K,
+                           float(min_opacity), _ptr(ws), ws_bytes)
+    L.check(lib.v3a_mcmc_relocate(C.byref(a), _stream()), "v3a_mcmc_relocate")
+
+
+def mcmc_noise(means: torch.Tensor, log_scales: torch.Tensor, quats: torch.Tensor, logits: torch.Tensor, *, scaler: float, seed: int,
+               step: int) -> None:
+    """The MCMC strategy's per-step noise, in place on means [U,3]: means += cov . (xi * gate * scaler), cov from (log_scales [U,3],
+    raw quats [U,4]) as splat_activate forms it, gate = sigmoid(-100 (opacity - 0.005)) of logits [U], xi three standard normals of
+    (seed, step, row) (csrc/mcmc.hip, v3a_mcmc_noise: fp64 after the loads, one rounding at the store)."""
+    U = logits.shape[0] if logits.dim() == 1 else 0
+    if U < 1:
+        raise ValueError("mcmc_noise: no Gaussians")
+    _f32_dev(means, "means", (U, 3))
+    _f32_dev(log_scales, "log_scales", (U, 3))
+    _f32_dev(quats, "quats", (U, 4))
+    _f32_dev(logits, "logits", (U,))
+    seed, step = _mcmc_key(seed, step, "mcmc_noise")
+    L.check(L.load().v3a_mcmc_noise(_ptr(means), _ptr(log_scales), _ptr(quats), _ptr(logits), U, float(scaler), seed, step, _stream()),
+            "v3a_mcmc_noise")

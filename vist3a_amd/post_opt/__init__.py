@@ -1,5 +1,5 @@
 """Post-optimisation of predicted Gaussians against their input views (the reference's
 third_party_model/anysplat/src/post_opt/simple_trainer.py), on the HIP rasteriser, loss and optimiser."""
-from .trainer import (PARAM_NAMES, PostOptConfig, bilagrid_learning_rate, create_splats, log_columns, post_optimize,  # noqa: F401
-                      random_backgrounds, train_view_order, train_views, view_order)
+from .trainer import (PARAM_NAMES, PostOptConfig, bilagrid_learning_rate, create_splats, log_columns, mcmc_growth, mcmc_refine,  # noqa: F401
+                      mcmc_refines_at, post_optimize, random_backgrounds, train_view_order, train_views, view_order)
 from .evaluate import evaluate_views  # noqa: F401

@@ -20,6 +20,13 @@ rasteriser's antialiased mode; cfg.random_bkgd (:326-327, :925-927) draws a fres
 cfg.scale_reg (:329-332, :966-977) add weight * mean sigmoid(logit) and weight * mean exp(log-scale), both from
 ops.splat_regularisers (one HIP reduction), only when the weight is above 0.
 
+cfg.strategy = "mcmc" is the reference's `mcmc` configuration (:1485-1501), gsplat's MCMCStrategy called at :1142-1150, restated in
+DESIGN.md section 7f (that text is the contract: gsplat is not in the reference tree).  After the Adam updates of a step, every
+cfg.mcmc_refine_every steps, Gaussians at or below cfg.mcmc_min_opacity are relocated onto live ones drawn by opacity
+(ops.mcmc_sample, ops.mcmc_relocate) and the scene grows by 5 % up to cfg.mcmc_cap_max; after every step ops.mcmc_noise adds
+opacity-gated, covariance-shaped noise to the means.  All of it is csrc/mcmc.hip with counter-based random numbers keyed by
+cfg.seed and the step, so two runs are bit-identical; nothing is read back.  With the default "none" the loop is as it was.
+
 The harmonics stay ONE [U,3,K] tensor: the reference's sh0 / shN optimisers (rates lr_sh and lr_sh / 20) are one ops.adam_step with
 a period of K, which is the same arithmetic because Adam is elementwise."""
 from __future__ import annotations
@@ -61,6 +68,13 @@ class PostOptConfig:
     random_bkgd: bool = False        # :326-327: a random background per step, to discourage transparency
     opacity_reg: float = 0.0         # :329-330: weight of mean sigmoid(logit), added when > 0
     scale_reg: float = 0.0           # :331-332: weight of mean exp(log-scale), added when > 0
+    strategy: str = "none"           # "none" (the reference's `default`: densification off, :389-392) or "mcmc" (:1485-1501)
+    mcmc_cap_max: int = 1_000_000    # gsplat MCMCStrategy's defaults from here on: the scene stops growing at this many Gaussians
+    mcmc_noise_lr: float = 5e5       # the noise is scaled by mcmc_noise_lr * (the means' current learning rate)
+    mcmc_refine_start_iter: int = 500
+    mcmc_refine_stop_iter: int = 25_000
+    mcmc_refine_every: int = 100
+    mcmc_min_opacity: float = 0.005  # at or below it a Gaussian is dead: relocated at the next refine
     test_every: int = 0              # k > 0: the views with index % k == 0 are held out of the loop (the reference's dataset split, test_every)
     # ours
     params: Tuple[str, ...] = ("means", "scales", "quats", "opacities", "sh0", "shN")
@@ -76,6 +90,25 @@ class PostOptConfig:
         if names & {"sh0", "shN"}:
             names = (names - {"sh0", "shN"}) | {"sh"}
         return tuple(n for n in PARAM_NAMES if n in names)
+
+    def check_strategy(self) -> None:
+        if self.strategy not in ("none", "mcmc"):
+            raise ValueError(f"PostOptConfig.strategy must be 'none' or 'mcmc', got {self.strategy!r}")
+        if self.strategy == "none":
+            return
+        ints = dict(mcmc_cap_max=self.mcmc_cap_max, mcmc_refine_start_iter=self.mcmc_refine_start_iter,
+                    mcmc_refine_stop_iter=self.mcmc_refine_stop_iter, mcmc_refine_every=self.mcmc_refine_every)
+        for name, n in ints.items():
+            if not isinstance(n, int) or isinstance(n, bool):
+                raise ValueError(f"PostOptConfig.{name} must be an integer, got {n!r}")
+        if self.mcmc_cap_max < 1 or self.mcmc_refine_every < 1:
+            raise ValueError(f"PostOptConfig.mcmc_cap_max and mcmc_refine_every must be positive, got {self.mcmc_cap_max!r} and "
+                             f"{self.mcmc_refine_every!r}")
+        if not self.mcmc_noise_lr >= 0 or not 0.0 < self.mcmc_min_opacity < 1.0:
+            raise ValueError(f"PostOptConfig.mcmc_noise_lr must be non-negative and mcmc_min_opacity in (0, 1), got "
+                             f"{self.mcmc_noise_lr!r} and {self.mcmc_min_opacity!r}")
+        if isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f"PostOptConfig.seed keys the strategy's random numbers: an integer in [0, 2^64), got {self.seed!r}")
 
     def check_bilagrid(self) -> None:
         if not self.use_bilateral_grid:
@@ -127,6 +160,45 @@ def log_columns(cfg: "PostOptConfig") -> list:
     return cols
 
 
+def mcmc_refines_at(cfg: PostOptConfig, i: int) -> bool:
+    """Whether the strategy refines (relocates and grows) after the Adam updates of 0-based step `i`: gsplat's
+    step > refine_start_iter and step < refine_stop_iter and step % refine_every == 0."""
+    return cfg.mcmc_refine_start_iter < i < cfg.mcmc_refine_stop_iter and i % cfg.mcmc_refine_every == 0
+
+
+def mcmc_growth(cfg: PostOptConfig, U: int) -> int:
+    """The Gaussians a refine adds to a scene of U: up to 5 %, never past cfg.mcmc_cap_max (a scene already above the cap only
+    relocates)."""
+    return max(0, min(cfg.mcmc_cap_max, int(1.05 * U)) - U)
+
+
+def mcmc_refine(splats: dict, cfg: PostOptConfig, t: int) -> None:
+    """One refine with `t` optimiser steps done: relocation (random stream 0), then growth (stream 1), in place on `splats`; the
+    tensors of params / m / v are REPLACED by longer ones when the scene grows.  Appends (relocated, added) to splats["mcmc_counts"],
+    int64 [refines,2] on the device."""
+    p, m, v = splats["params"], splats["m"], splats["v"]
+    U, dev = p["means"].shape[0], p["means"].device
+    with torch.no_grad():
+        _, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        src, counts = ops.mcmc_sample(op, min_weight=cfg.mcmc_min_opacity, alive_only=True, n_slots=U, seed=cfg.seed,
+                                      stream=ops.MCMC_STREAMS["relocate"], step=t)
+        ops.mcmc_relocate(src, counts, p, m, v, dst_offset=0, min_opacity=cfg.mcmc_min_opacity)
+        relocated = (src >= 0).sum()
+        n = mcmc_growth(cfg, U)
+        if n > 0:
+            _, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])      # of the relocated state
+            src, counts = ops.mcmc_sample(op, min_weight=cfg.mcmc_min_opacity, alive_only=False, n_slots=n, seed=cfg.seed,
+                                          stream=ops.MCMC_STREAMS["grow"], step=t)
+            for d in (p, m, v):
+                for name in PARAM_NAMES:
+                    old = d[name].detach()
+                    d[name] = torch.zeros((U + n,) + tuple(old.shape[1:]), device=dev, dtype=old.dtype)
+                    d[name][:U].copy_(old)
+            ops.mcmc_relocate(src, counts, p, m, v, dst_offset=U, min_opacity=cfg.mcmc_min_opacity)
+        row = torch.stack([relocated, torch.full((), n, device=dev, dtype=torch.int64)])[None]
+        splats["mcmc_counts"] = torch.cat([splats["mcmc_counts"], row]) if "mcmc_counts" in splats else row
+
+
 def train_views(n_views: int, test_every: int) -> list:
     """The views the loop may show: all of them, or with test_every = k > 0 those with index % k != 0 (the others are held out for
     post_opt.evaluate_views, as the reference's parser splits its dataset)."""
@@ -154,7 +226,8 @@ def _single(gaussians: Gaussians) -> None:
 
 
 def create_splats(gaussians: Gaussians, cfg: PostOptConfig, n_views: Optional[int] = None) -> dict:
-    """-> {"params": {name: f32 tensor}, "m": {...}, "v": {...}, "step": 0, "keep": bool [U] (the rows kept)}.  scales are stored as
+    """-> {"params": {name: f32 tensor}, "m": {...}, "v": {...}, "step": 0, "keep": bool [U] (the rows kept)}.  "keep" describes
+    creation only: which of the input's Gaussians became rows; the MCMC strategy later moves and adds rows and leaves it alone.  scales are stored as
     logs, opacities as logits (clamped to 1 - 1e-6 so that the logit is finite), quaternions as they come (xyzw, as `Gaussians` keeps them).
     With cfg.use_bilateral_grid and `n_views`, also "bil_grids" (identity, f32 [n_views,L,GY,GX,12]) and its moments "bil_m", "bil_v"."""
     _single(gaussians)
@@ -224,9 +297,19 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     random_backgrounds(steps, cfg.seed)[i]; the target image is not composited over it (as in the reference), and the render is
     clamped to [0,1] AFTER the background went in (the reference adds it to an unclamped render: a deviation).  cfg.opacity_reg /
     cfg.scale_reg > 0 add weight * ops.splat_regularisers(...) terms to the loss and, each, one last log column with the unweighted
-    mean, opacity before scale, after every other column (log_columns(cfg) names them all)."""
+    mean, opacity before scale, after every other column (log_columns(cfg) names them all).
+
+    With cfg.strategy = "mcmc", after the Adam updates of the step with i steps done before it: if mcmc_refines_at(cfg, i),
+    mcmc_refine (relocation, then growth by mcmc_growth rows: the tensors in `splats` are replaced by longer ones and the returned
+    Gaussians follow the new count); then, on every step, ops.mcmc_noise on the means with scaler = cfg.mcmc_noise_lr * the means'
+    rate after the step.  The random numbers are keyed by cfg.seed and the steps done, so with `splats` carried through several calls
+    the STRATEGY continues where one call would be: its random numbers, the timing of its refines and the grown tensors.  The view
+    order and the random backgrounds restart with every call, as they always did, so several calls equal one call only where
+    those repeat.  splats["mcmc_counts"], int64 [refines,2] on the device, holds (relocated, added) of every refine;
+    nothing is read back.  The reference pairs the strategy with opacity_reg = scale_reg = 0.01; neither default changes here."""
     cfg = cfg or PostOptConfig()
     cfg.check_bilagrid()
+    cfg.check_strategy()
     _single(gaussians)
     for t, n in ((extrinsics, "extrinsics"), (intrinsics, "intrinsics")):
         if t.requires_grad:
@@ -278,6 +361,7 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     lrs = dict(means=cfg.lr_means, scales=cfg.lr_scales, quats=cfg.lr_quats, opacities=cfg.lr_opacities, sh=cfg.lr_sh)
     decay = 0.01 ** (1.0 / cfg.max_steps)
     ws = ops.GsWorkspace()
+    mcmc = cfg.strategy == "mcmc"
     leaves = [p[n].requires_grad_(True) for n in trained]
     if bil:
         leaves.append(splats["bil_grids"].requires_grad_(True))
@@ -321,6 +405,12 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
                 if bil:   # every view's grid moves each step through the TV term, as in the reference
                     ops.adam_step(splats["bil_grids"], grads[-1].contiguous(), splats["bil_m"], splats["bil_v"],
                                   lr=bilagrid_learning_rate(cfg, t - 1), step=t, betas=cfg.betas, eps=1e-15, period=0)
+                if mcmc:
+                    if mcmc_refines_at(cfg, t - 1):
+                        mcmc_refine(splats, cfg, t)
+                        leaves = [p[n].requires_grad_(True) for n in trained] + leaves[len(trained):]    # a grown scene has new tensors
+                    ops.mcmc_noise(p["means"], p["scales"], p["quats"], p["opacities"], scaler=cfg.mcmc_noise_lr * (cfg.lr_means * decay ** t),
+                                   seed=cfg.seed, step=t)
             splats["step"] = t
     finally:
         for n in trained:

@@ -60,6 +60,14 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
                    help="weight of the mean opacity in the post-optimisation loss (the reference's opacity_reg); 0 = off")
     g.add_argument("--post_opt_scale_reg", type=float, default=0.0, metavar="X",
                    help="weight of the mean scale in the post-optimisation loss (the reference's scale_reg); 0 = off")
+    g.add_argument("--post_opt_mcmc", action="store_true",
+                   help="post-optimise with the MCMC strategy (the reference's `mcmc` configuration): dead Gaussians are relocated onto live "
+                        "ones and the scene grows by 5 %% at every refine, opacity-gated noise moves the means after every step.  The "
+                        "reference pairs it with --post_opt_opacity_reg 0.01 --post_opt_scale_reg 0.01; this switch does not set them")
+    g.add_argument("--post_opt_mcmc_cap_max", type=int, default=1_000_000, metavar="N",
+                   help="the MCMC strategy stops adding Gaussians at N (a scene already above N only relocates)")
+    g.add_argument("--post_opt_mcmc_refine", type=str, default="500,25000,100", metavar="START,STOP,EVERY",
+                   help="the MCMC strategy refines after the steps i with START < i < STOP and i %% EVERY == 0 (counted from 0)")
     g.add_argument("--post_opt_eval_every", type=int, default=0, metavar="K",
                    help="hold the views with index %% K == 0 out of the post-optimisation (the reference's test_every) and evaluate them "
                         "before and after it: PSNR, SSIM, the number of Gaussians and a time per image - with --post_opt_bilateral_grid "
