@@ -38,7 +38,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 31) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 32) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -503,8 +503,9 @@ int v3a_gs_rasterize(const v3a_gs_rasterize_args* a, void* stream);
 /* ---- Backward of the two stages (csrc/raster_bwd.hip): what gsplat's rasterize_to_pixels_bwd, fully_fused_projection_bwd and
  * spherical_harmonics_bwd hand torch.autograd for the call above.  fp32; no float atomics: every sum has a fixed order, so results
  * are bit-identical run to run.  The radius, culling, binning and early-stop decisions of the forward are constants, as in gsplat.
- * NOT computed: gradients to viewmat / campos / K (gsplat's optional pose gradients; the reference leaves cam_rot_delta /
- * cam_trans_delta unused), cov_ignore=True (quaternion / scale input), packed mode.
+ * Gradients to viewmat / campos (gsplat's optional pose gradients, which the reference's pose optimiser trains through) come from
+ * v3a_gs_project_backward_cam only.  NOT computed: the gradient to K (the reference does not optimise intrinsics), cov_ignore=True
+ * (quaternion / scale input), packed mode.
  * Antialiased mode (rasterize_mode 1 above): stage 2 differentiates with respect to an entry's EFFECTIVE opacity
  * opacities[g] * compensations[c,g]; stage 1 splits that into the opacity's share and the compensation's, whose gradient
  * d comp / d Sigma2 = ((1 - comp^2) B^-1 - eps2d det(B^-1) I) / (2 comp)  (Sigma2 = J Cc J^T, B = Sigma2 + eps2d I, B^-1 the conic;
@@ -566,6 +567,20 @@ typedef struct {
                                comp itself is recomputed from the scene, as everything else here, not read from memory */
 } v3a_gs_project_backward_args;
 int v3a_gs_project_backward(const v3a_gs_project_backward_args* a, void* stream);
+
+/* Stage 1 backward WITH camera gradients: `a` and its four outputs exactly as above (bit-identical: the same kernel writes them,
+ * a second instantiation then evaluates the projection chain again for the camera terms), plus, per camera c with
+ * viewmat = [R | t]:   dL/dt = sum_g v_c,   dL/dR = sum_g (v_c m_g^T + 2 W R S_g),   dL/dcampos = -sum_g dL/dd
+ * (v_c = the camera-space mean gradient, W = dL/d(R S R^T), d = m_g - campos, the SH view direction; its term is 0 where
+ * |d| < 1e-20, as for the means).  d_viewmat [C,4,4]: all 16 entries written, the bottom row as zeros; d_campos [C,3].  No float
+ * atomics: every entry's 15 fp32 terms are converted (exactly) to fp64, summed over the wave of 64 Gaussians in a fixed order
+ * into one partial row of `workspace` ([C, ceil(U / 64), 15] doubles, 8-byte aligned), and a second launch adds each camera's
+ * rows in a fixed order and rounds ONCE to fp32.  Entries with radii == 0 contribute exact zeros.  Too small a workspace: -4.
+ * `workspace` must be a non-null, 8-byte aligned pointer even for U == 0, where the queried size is 0 and nothing is read (-1
+ * otherwise): with U == 0 the outputs are written as exact zeros. */
+long v3a_gs_project_backward_cam_workspace_bytes(long U, int C);   /* V3A_ERR_SHAPE for U < 0, U >= 2^31 or C < 1 */
+int v3a_gs_project_backward_cam(const v3a_gs_project_backward_args* a, float* d_viewmat, float* d_campos, void* workspace,
+                                long workspace_bytes, void* stream);
 
 /* ---- Image-pair metrics of the novel-view-synthesis evaluation (calculate_metric.py; anysplat/src/evaluation/metrics.py:11-55):
  * per pair, SSIM as skimage.metrics.structural_similarity(win_size=11, gaussian_weights=True, channel_axis=0, data_range=1.0)
@@ -783,6 +798,20 @@ typedef struct {
   double beta1, beta2, eps, bias_correction1, bias_correction2;
 } v3a_adam_args;
 int v3a_adam_step(const v3a_adam_args* a, void* stream);
+
+/* The pose optimiser's parametrisation (csrc/post_opt.hip; post_opt/utils.py:12-48 CameraOptModule, :117-138): per camera 9
+ * deltas (dx[3], drot[6]); a1 = drot[0..2] + (1,0,0), a2 = drot[3..5] + (0,1,0), b1 = a1 / max(|a1|, 1e-12),
+ * b2 = normalise(a2 - (b1 . a2) b1) with the same clamp, b3 = b1 x b2, Rd = the matrix with ROWS b1, b2, b3, and the adjusted
+ * camera is c2w' = c2w_base [Rd | dx].  What the rasteriser takes follows in closed form from the base matrices [V,4,4]:
+ *   viewmat [V,4,4] = inverse(c2w') = [Rd^T | -Rd^T dx] w2c_base,     campos [V,3] = c2w'[:3,3] = c2w_base[:3,:3] dx + c2w_base[:3,3].
+ * One thread per camera, fp64 after the loads, one rounding at the store; zero deltas return the base matrices bit for bit
+ * (every product is by exactly 1 or 0).  Backward: (d_viewmat [V,4,4], d_campos [V,3]) -> d_deltas [V,9], closed form through
+ * the product and the Gram-Schmidt steps, every element written once, exactly linear in the incoming gradients; the bottom row
+ * of d_viewmat is not read (viewmat's is the base's).  1 <= V <= 2^24 (V3A_ERR_SHAPE otherwise). */
+int v3a_camera_adjust(const float* w2c_base, const float* c2w_base, const float* deltas, int V, float* viewmat, float* campos,
+                      void* stream);
+int v3a_camera_adjust_backward(const float* w2c_base, const float* c2w_base, const float* deltas, const float* d_viewmat,
+                               const float* d_campos, int V, float* d_deltas, void* stream);
 
 /* The post-optimisation loop's two regularisers (csrc/splat_reg.hip; simple_trainer.py:966-977): from opacity logits f32 [U] and
  * log-scales f32 [U,3], out f64 [2] = (mean sigmoid(logit), mean exp(log_scale)) - the reference's abs() is the identity on both.

@@ -65,14 +65,17 @@ def build_text_encoder(args, device):
 
 
 def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False, eval_every=0, lpips=None,
-           antialiased=False, random_bkgd=False, opacity_reg=0.0, scale_reg=0.0, mcmc=None):
+           antialiased=False, random_bkgd=False, opacity_reg=0.0, scale_reg=0.0, mcmc=None, pose_opt=False, pose_lr=None,
+           cameras_out=None):
     """-> (refined Gaussians, stats or None).  With eval_every = K > 0 the views with index % K == 0 are held out of the loop and
     scored before and after it: stats = {"before": {...}, "after": {...}, "held_out": [...]} (vist3a_amd.post_opt.evaluate_views).
     antialiased / random_bkgd / opacity_reg / scale_reg: the PostOptConfig fields of those names; the evaluation renders in the
     loop's rasterize mode.  mcmc: None, or (cap_max, (start, stop, every)) to run the loop with cfg.strategy = "mcmc"; the refined
-    scene then has as many Gaussians as the strategy left it with."""
+    scene then has as many Gaussians as the strategy left it with.  pose_opt / pose_lr: cfg.pose_opt and cfg.pose_opt_lr (None: its
+    default) - scene and cameras are refined together, and the dict `cameras_out` (if given) receives "extrinsics" (the adjusted
+    camera-to-world matrix of every view, held-out views as given), "deltas" [Vt,9] and "train_views", as lists."""
     from vist3a_amd import ops
-    from vist3a_amd.post_opt import PostOptConfig, evaluate_views, post_optimize, train_views
+    from vist3a_amd.post_opt import PostOptConfig, adjusted_extrinsics, create_splats, evaluate_views, post_optimize, train_views
     with torch.no_grad():
         ff = ops.bilinear_cl(clip_cl, (res, res), align_corners=False)          # what Text23DGS.generate fed the reconstruction
         frames = ((ff[..., :3].float() + 1) / 2).clamp(0, 1).contiguous()       # [V,res,res,3] in [0,1]
@@ -94,6 +97,9 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
     if mcmc is not None:
         cfg.strategy, cfg.mcmc_cap_max = "mcmc", int(mcmc[0])
         cfg.mcmc_refine_start_iter, cfg.mcmc_refine_stop_iter, cfg.mcmc_refine_every = (int(x) for x in mcmc[1])
+    cfg.pose_opt = bool(pose_opt)
+    if pose_lr is not None:
+        cfg.pose_opt_lr = float(pose_lr)
     ext, intr = pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach()
     stats = None
     if cfg.test_every > 0:
@@ -102,7 +108,15 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
         score = lambda gs: evaluate_views(gs, frames[held].contiguous(), ext[held], intr[held], color_correct=cfg.use_bilateral_grid,
                                           lpips=lpips, antialiased=cfg.antialiased)
         stats = dict(before=score(gaussians), held_out=held)
-    g, _ = post_optimize(gaussians, frames, ext, intr, cfg, steps=steps, **extra)
+    if cfg.pose_opt:   # the loop's state is kept: the trained deltas are in it
+        tv = train_views(frames.shape[0], cfg.test_every)
+        splats = create_splats(gaussians, cfg, len(tv))
+        g, _ = post_optimize(gaussians, frames, ext, intr, cfg, steps=steps, splats=splats, **extra)
+        if cameras_out is not None:
+            cameras_out.update(extrinsics=adjusted_extrinsics(ext, splats, cfg).cpu().tolist(), deltas=splats["pose_deltas"].cpu().tolist(),
+                               train_views=tv)
+    else:
+        g, _ = post_optimize(gaussians, frames, ext, intr, cfg, steps=steps, **extra)
     if stats is not None:
         stats = dict(before=stats["before"], after=score(g), held_out=stats["held_out"])
     return g, stats
@@ -150,6 +164,10 @@ def main(args):
     if args.post_opt_opacity_reg < 0 or args.post_opt_scale_reg < 0:
         raise ValueError("--post_opt_opacity_reg and --post_opt_scale_reg are weights >= 0")
     mcmc = mcmc_options(args)
+    if (args.post_opt_pose_opt or args.post_opt_pose_lr is not None) and args.post_opt_steps <= 0:
+        raise ValueError("--post_opt_pose_opt / --post_opt_pose_lr need --post_opt_steps > 0 (the poses are refined by the post-optimisation)")
+    if args.post_opt_pose_lr is not None and not args.post_opt_pose_lr > 0:
+        raise ValueError("--post_opt_pose_lr must be positive")
     if (args.lpips_vgg_weights is None) != (args.lpips_lin_weights is None):
         raise ValueError("--lpips_vgg_weights and --lpips_lin_weights go together: give both or neither")
     lpips = None
@@ -176,12 +194,16 @@ def main(args):
         (save / "prompt.txt").write_text(prompt)
         g = out.gaussians
         if args.post_opt_steps > 0:   # against the frames the reconstruction saw, at the predicted context poses and intrinsics
+            cameras = {}
             g, stats = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps, out.depth_dict,
                               args.post_opt_depth_lambda, args.post_opt_bilateral_grid, args.post_opt_eval_every, lpips,
                               antialiased=args.post_opt_antialiased, random_bkgd=args.post_opt_random_bkgd,
-                              opacity_reg=args.post_opt_opacity_reg, scale_reg=args.post_opt_scale_reg, mcmc=mcmc)
+                              opacity_reg=args.post_opt_opacity_reg, scale_reg=args.post_opt_scale_reg, mcmc=mcmc,
+                              pose_opt=args.post_opt_pose_opt, pose_lr=args.post_opt_pose_lr, cameras_out=cameras)
             if stats is not None:
                 (save / "post_opt_stats.json").write_text(json.dumps(stats, indent=1))
+            if args.post_opt_pose_opt:   # the refined cameras; the videos below keep the predicted path, as the reference's trajectory does
+                (save / "post_opt_cameras.json").write_text(json.dumps(cameras, indent=1))
         if not args.no_video:  # orbit video through the predicted context poses (reference :144-154)
             decoder = stitched.stitched_3d_model.decoder
             mode = decoder.rasterize_mode

@@ -11,7 +11,12 @@ of ref per workgroup row, 3 x 16 B per pixel) over its time.  It runs outside th
 With --mcmc a third JSON line times the MCMC strategy (csrc/mcmc.hip) on the same Gaussians: the per-step noise (ops.mcmc_noise, 44 B
 read and 12 B written per Gaussian) against a `copy_` of the same 56 B per Gaussian, and one refine's pieces - the relocation sampler and
 relocation with 10 % of the scene dead, the growth sampler for 5 % more rows and the growth itself (the reallocation of the fifteen
-tensors is the caller's torch work and is not timed)."""
+tensors is the caller's torch work and is not timed).
+With --pose_opt a further JSON line times pose optimisation (cfg.pose_opt) on the same scene and camera: the whole step with the
+camera adjusted through ops.camera_adjust and rendered with camera_grad=True (the deltas one more leaf, their Adam included), the
+projection-backward call alone without and with camera gradients (the second is the plain kernel + the CAM kernel + the finish
+kernel: the projection chain runs twice), and the two camera_adjust launches.  The kernels inside the camera-gradient call are
+told apart with a kernel trace of this tool, not here."""
 import argparse
 import json
 import math
@@ -32,6 +37,7 @@ def main():
     ap.add_argument("--antialiased", action="store_true", help="the loop's renders in the rasteriser's antialiased mode")
     ap.add_argument("--bilateral_grid", action="store_true")
     ap.add_argument("--mcmc", action="store_true", help="also time the MCMC strategy's noise launch and the pieces of one refine")
+    ap.add_argument("--pose_opt", action="store_true", help="also time the step with pose optimisation and the camera-gradient launches")
     a = ap.parse_args()
     from vist3a_amd import ops
     U, W, H = a.gaussians, a.size, a.size
@@ -120,6 +126,71 @@ def main():
                           color_correct_read_GBps=round(5 * 48 * W * H / f_ms / 1e6, 1), image_mse_ms=round(m_ms, 3))))
     if a.mcmc:
         print(json.dumps(mcmc_times(ops, {k: t.detach() for k, t in p.items()}, m, v, a.warmup, a.iters)))
+    if a.pose_opt:
+        print(json.dumps(pose_times(ops, p, view, K, target, bg, ws, W, H, "antialiased" if a.antialiased else "classic", a.warmup, a.iters)))
+
+
+def pose_times(ops, p, view, K, target, bg, ws, W, H, mode, warmup, iters):
+    U = p["means"].shape[0]
+    w2c = view.contiguous()
+    c2w = torch.linalg.inv(view.cpu()).contiguous().cuda()
+    deltas = (torch.randn(1, 9, generator=torch.Generator().manual_seed(3)) * 1e-3).cuda().requires_grad_(True)
+    dm, dv = torch.zeros_like(deltas), torch.zeros_like(deltas)
+    timed = {}
+
+    def clock(name, fn):
+        ms = []
+        for it in range(warmup + iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(it)
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                ms.append(e0.elapsed_time(e1))
+        timed[name] = statistics.median(ms)
+        return out
+
+    def step(it):   # forward + backward of a pose-optimising step, and the deltas' Adam (the splat tensors' Adam is the plain step's)
+        cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        v_, c_ = ops.camera_adjust(w2c, c2w, deltas)
+        col, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, v_, c_, K, W, H, background=bg, clamp_rgb=True, workspace=ws,
+                                  rasterize_mode=mode, camera_grad=True)
+        loss, _, _ = ops.photometric_loss(col, target, 0.2)
+        grads = torch.autograd.grad(loss, list(p.values()) + [deltas])
+        with torch.no_grad():
+            ops.adam_step(deltas, (grads[-1] + 1e-6 * deltas).contiguous(), dm, dv, lr=1e-5, step=it + 1, eps=1e-8)
+
+    def step_plain(it):   # the same without pose optimisation and without the splat tensors' Adam: the difference is what pose_opt adds
+        cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        col, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, view, campos_of(view), K, W, H, background=bg, clamp_rgb=True, workspace=ws,
+                                  rasterize_mode=mode)
+        loss, _, _ = ops.photometric_loss(col, target, 0.2)
+        torch.autograd.grad(loss, list(p.values()))
+
+    campos0 = c2w[:, :3, 3].contiguous()
+    campos_of = lambda _: campos0
+    clock("step_pose_fwd_bwd", step)
+    clock("step_plain_fwd_bwd", step_plain)
+    with torch.no_grad():
+        cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        means, sh = p["means"].detach(), p["sh"].detach()
+        pr = ops.gs_project(means, cov, sh, view, campos0, K, W, H, rasterize_mode=mode)
+        r = ops.gs_rasterize(pr, op, W, H, background=bg, workspace=ws, return_order=True)
+        eg = ops.gs_rasterize_backward(pr, op, W, H, r["tile_offsets"], r["flatten_ids"].contiguous(), torch.rand(1, H, W, 3, device="cuda"),
+                                       torch.zeros(1, H, W, device="cuda"), torch.zeros(1, H, W, device="cuda"), background=bg)
+        aa = dict(rasterize_mode=mode, opacities=op if mode == "antialiased" else None)
+        clock("project_backward", lambda it: ops.gs_project_backward(means, cov, sh, view, campos0, K, W, H, pr["radii"], eg, **aa))
+        clock("project_backward_cam", lambda it: ops.gs_project_backward(means, cov, sh, view, campos0, K, W, H, pr["radii"], eg,
+                                                                         camera_grad=True, **aa))
+        d = deltas.detach()
+        clock("camera_adjust", lambda it: ops.camera_adjust(w2c, c2w, d))
+        lib, p_ = ops.L.load(), ops._ptr
+        gv, gc, gd = torch.rand(1, 4, 4, device="cuda"), torch.rand(1, 3, device="cuda"), torch.empty(1, 9, device="cuda")
+        clock("camera_adjust_backward", lambda it: lib.v3a_camera_adjust_backward(p_(w2c), p_(c2w), p_(d), p_(gv), p_(gc), 1, p_(gd), ops._stream()))
+    return dict(gaussians=U, size=W, visible=int((pr["radii"] > 0).sum()), cam_workspace_bytes=120 * ((U + 63) // 64),
+                **{k + "_ms": round(x, 4) for k, x in timed.items()},
+                cam_over_plain=round(timed["project_backward_cam"] / timed["project_backward"], 2))
 
 
 def mcmc_times(ops, p, m, v, warmup, iters):

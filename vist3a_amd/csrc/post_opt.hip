@@ -7,6 +7,9 @@
 //                      order, internal normalisation and the product are those of gaussian_adapter_kernel (elementwise.hip).
 //   fused Adam         torch.optim.Adam's update on one parameter tensor per launch (simple_trainer.py:442-460: one optimiser per
 //                      tensor, eps 1e-15), in place.
+//   camera adjust      the pose optimiser's parametrisation (post_opt/utils.py:12-48, :117-138): 9 deltas per camera (translation +
+//                      6D rotation) -> the adjusted view matrix and camera centre, forward and backward, in closed form (no matrix
+//                      inverse on the device, nothing read back).
 #include "common.h"
 #include "splat_quat.h"   // quat_R: the rotation of a raw quaternion, shared with mcmc.hip
 #include "../../include/vist3a_hip.h"
@@ -141,7 +144,128 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamP a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- camera pose deltas
+// The rotation of a 6D delta (utils.py:117-138): a1 = r[0..2] + (1,0,0), a2 = r[3..5] + (0,1,0); b1 = a1 / max(|a1|, 1e-12),
+// u = a2 - (b1 . a2) b1, b2 = u / max(|u|, 1e-12), b3 = b1 x b2.  Rd has the ROWS b1, b2, b3.
+struct Gram {
+  double a2[3], b1[3], b2[3], b3[3], u[3], n1, nu, l1, lu, s;   // l = the norms, n = their clamped values, s = b1 . a2
+};
+
+__device__ __forceinline__ Gram gram_schmidt(const float* r) {
+  Gram q;
+  const double a1[3] = {(double)r[0] + 1.0, (double)r[1], (double)r[2]};
+  q.a2[0] = (double)r[3]; q.a2[1] = (double)r[4] + 1.0; q.a2[2] = (double)r[5];
+  q.l1 = sqrt(a1[0] * a1[0] + a1[1] * a1[1] + a1[2] * a1[2]);
+  q.n1 = fmax(q.l1, 1e-12);
+  for (int i = 0; i < 3; ++i) q.b1[i] = a1[i] / q.n1;
+  q.s = q.b1[0] * q.a2[0] + q.b1[1] * q.a2[1] + q.b1[2] * q.a2[2];
+  for (int i = 0; i < 3; ++i) q.u[i] = q.a2[i] - q.s * q.b1[i];
+  q.lu = sqrt(q.u[0] * q.u[0] + q.u[1] * q.u[1] + q.u[2] * q.u[2]);
+  q.nu = fmax(q.lu, 1e-12);
+  for (int i = 0; i < 3; ++i) q.b2[i] = q.u[i] / q.nu;
+  q.b3[0] = q.b1[1] * q.b2[2] - q.b1[2] * q.b2[1];
+  q.b3[1] = q.b1[2] * q.b2[0] - q.b1[0] * q.b2[2];
+  q.b3[2] = q.b1[0] * q.b2[1] - q.b1[1] * q.b2[0];
+  return q;
+}
+
+// c2w' = c2w_base [Rd | dx]  ->  viewmat = inverse(c2w') = [Rd^T | -Rd^T dx] w2c_base,  campos = c2w'[:3,3] = R_c2w dx + t_c2w.
+// One thread per camera, fp64 after the loads, one rounding at the store.  A zero delta gives Rd = I exactly and every product
+// below is by exactly 1 or 0: the outputs are then the base matrices.
+__global__ void __launch_bounds__(64) camera_adjust_kernel(const float* __restrict__ w2c, const float* __restrict__ c2w,
+                                                           const float* __restrict__ deltas, int V, float* __restrict__ viewmat,
+                                                           float* __restrict__ campos) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= V) return;
+  const float* d = deltas + 9 * c;
+  const Gram q = gram_schmidt(d + 3);
+  const double dx[3] = {(double)d[0], (double)d[1], (double)d[2]};
+  const double* b[3] = {q.b1, q.b2, q.b3};
+  const float* Wm = w2c + 16 * c;
+  const float* Cm = c2w + 16 * c;
+  for (int i = 0; i < 3; ++i) {
+    // row i of [Rd^T | p]:  Rd^T[i][k] = b_k[i],  p = -Rd^T dx
+    const double n0 = b[0][i], n1 = b[1][i], n2 = b[2][i];
+    const double p = -(n0 * dx[0] + n1 * dx[1] + n2 * dx[2]);
+    for (int j = 0; j < 4; ++j)
+      viewmat[16 * c + 4 * i + j] =
+          (float)(n0 * (double)Wm[j] + n1 * (double)Wm[4 + j] + n2 * (double)Wm[8 + j] + p * (double)Wm[12 + j]);
+    campos[3 * c + i] = (float)((double)Cm[4 * i] * dx[0] + (double)Cm[4 * i + 1] * dx[1] + (double)Cm[4 * i + 2] * dx[2] + (double)Cm[4 * i + 3]);
+  }
+  for (int j = 0; j < 4; ++j) viewmat[16 * c + 12 + j] = Wm[12 + j];
+}
+
+// Backward of the above: (dL/dviewmat [V,4,4], dL/dcampos [V,3]) -> dL/ddeltas [V,9], every element written once, linear in the
+// incoming gradients.  viewmat's bottom row is the base's: no gradient passes through it.
+__global__ void __launch_bounds__(64) camera_adjust_bwd_kernel(const float* __restrict__ w2c, const float* __restrict__ c2w,
+                                                               const float* __restrict__ deltas, const float* __restrict__ d_viewmat,
+                                                               const float* __restrict__ d_campos, int V, float* __restrict__ d_deltas) {
+  const int c = blockIdx.x * 64 + threadIdx.x;
+  if (c >= V) return;
+  const float* d = deltas + 9 * c;
+  const Gram q = gram_schmidt(d + 3);
+  const double dx[3] = {(double)d[0], (double)d[1], (double)d[2]};
+  const float* Wm = w2c + 16 * c;
+  const float* Cm = c2w + 16 * c;
+  const float* G = d_viewmat + 16 * c;
+  // A = [Rd^T | p] (top three rows):  dL/dA = G w2c^T
+  double gA[3][4];
+  for (int i = 0; i < 3; ++i)
+    for (int k = 0; k < 4; ++k)
+      gA[i][k] = (double)G[4 * i] * (double)Wm[4 * k] + (double)G[4 * i + 1] * (double)Wm[4 * k + 1] +
+                 (double)G[4 * i + 2] * (double)Wm[4 * k + 2] + (double)G[4 * i + 3] * (double)Wm[4 * k + 3];
+  // p = -Rd^T dx:  dL/d(Rd^T)[i][k] += -gp[i] dx[k],  dL/ddx = -Rd gp;  campos = R_c2w dx + t:  dL/ddx += R_c2w^T g_campos
+  double gb[3][3];   // gb[k] = dL/db_k (row k of Rd):  Rd^T[i][k] = b_k[i]
+  for (int k = 0; k < 3; ++k)
+    for (int i = 0; i < 3; ++i) gb[k][i] = gA[i][k] - gA[i][3] * dx[k];
+  const double* b[3] = {q.b1, q.b2, q.b3};
+  const double gc[3] = {(double)d_campos[3 * c], (double)d_campos[3 * c + 1], (double)d_campos[3 * c + 2]};
+  double out[9];
+  for (int k = 0; k < 3; ++k)
+    out[k] = -(b[k][0] * gA[0][3] + b[k][1] * gA[1][3] + b[k][2] * gA[2][3]) +
+             ((double)Cm[k] * gc[0] + (double)Cm[4 + k] * gc[1] + (double)Cm[8 + k] * gc[2]);
+  // b3 = b1 x b2:  dL/db1 += b2 x g3,  dL/db2 += g3 x b1
+  const double* g3 = gb[2];
+  gb[0][0] += q.b2[1] * g3[2] - q.b2[2] * g3[1]; gb[0][1] += q.b2[2] * g3[0] - q.b2[0] * g3[2]; gb[0][2] += q.b2[0] * g3[1] - q.b2[1] * g3[0];
+  gb[1][0] += g3[1] * q.b1[2] - g3[2] * q.b1[1]; gb[1][1] += g3[2] * q.b1[0] - g3[0] * q.b1[2]; gb[1][2] += g3[0] * q.b1[1] - g3[1] * q.b1[0];
+  // b2 = u / max(|u|, eps): the clamp passes the norm's gradient where |u| >= eps
+  double gu[3];
+  {
+    const double dot = q.lu >= 1e-12 ? q.b2[0] * gb[1][0] + q.b2[1] * gb[1][1] + q.b2[2] * gb[1][2] : 0.0;
+    for (int i = 0; i < 3; ++i) gu[i] = (gb[1][i] - q.b2[i] * dot) / q.nu;
+  }
+  // u = a2 - s b1, s = b1 . a2
+  const double gs = -(gu[0] * q.b1[0] + gu[1] * q.b1[1] + gu[2] * q.b1[2]);
+  for (int i = 0; i < 3; ++i) {
+    out[6 + i] = gu[i] + gs * q.b1[i];
+    gb[0][i] += -q.s * gu[i] + gs * q.a2[i];
+  }
+  {
+    const double dot = q.l1 >= 1e-12 ? q.b1[0] * gb[0][0] + q.b1[1] * gb[0][1] + q.b1[2] * gb[0][2] : 0.0;
+    for (int i = 0; i < 3; ++i) out[3 + i] = (gb[0][i] - q.b1[i] * dot) / q.n1;
+  }
+  for (int i = 0; i < 9; ++i) d_deltas[9 * c + i] = (float)out[i];
+}
+
 }  // namespace
+
+extern "C" int v3a_camera_adjust(const float* w2c_base, const float* c2w_base, const float* deltas, int V, float* viewmat, float* campos,
+                                 void* stream) {
+  if (!w2c_base || !c2w_base || !deltas || !viewmat || !campos) return V3A_ERR_ARG;
+  if (V < 1 || V > (1 << 24)) return V3A_ERR_SHAPE;
+  hipLaunchKernelGGL(camera_adjust_kernel, dim3((unsigned)((V + 63) / 64)), dim3(64), 0, (hipStream_t)stream, w2c_base, c2w_base, deltas, V,
+                     viewmat, campos);
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}
+
+extern "C" int v3a_camera_adjust_backward(const float* w2c_base, const float* c2w_base, const float* deltas, const float* d_viewmat,
+                                          const float* d_campos, int V, float* d_deltas, void* stream) {
+  if (!w2c_base || !c2w_base || !deltas || !d_viewmat || !d_campos || !d_deltas) return V3A_ERR_ARG;
+  if (V < 1 || V > (1 << 24)) return V3A_ERR_SHAPE;
+  hipLaunchKernelGGL(camera_adjust_bwd_kernel, dim3((unsigned)((V + 63) / 64)), dim3(64), 0, (hipStream_t)stream, w2c_base, c2w_base, deltas,
+                     d_viewmat, d_campos, V, d_deltas);
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}
 
 extern "C" int v3a_splat_activate(const float* log_scales, const float* quats, const float* logits, long U, float* covars,
                                   float* opacities, void* stream) {

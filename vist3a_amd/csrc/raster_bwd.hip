@@ -1,6 +1,7 @@
 // Backward of the 3D-Gaussian rasteriser (raster.hip) for gfx950, fp32: what gsplat's rasterize_to_pixels_bwd +
 // fully_fused_projection_bwd + spherical_harmonics_bwd give torch.autograd, for the same call the forward replaces
-// (RGB+D, classic or antialiased, packed=False, explicit world covariances).  Gradients reach means, covars, sh and opacities; cameras are constants.
+// (RGB+D, classic or antialiased, packed=False, explicit world covariances).  Gradients reach means, covars, sh and opacities; cameras are
+// constants unless v3a_gs_project_backward_cam is called, which also returns dL/d(viewmat, campos).
 //
 //   v3a_gs_rasterize_backward   count + rocPRIM scan (the forward's, re-run: each camera-Gaussian entry's first row slot) ->
 //                               gs_blend_bwd_kernel, one 256-lane workgroup per 16x16 tile of every camera: walks the tile's
@@ -14,8 +15,13 @@
 //                               the depth channel and the SH view direction; SH coefficients.  Antialiased mode: the entry's
 //                               dL/d(opacity * comp) splits into the opacity's share (x comp) and dL/dcomp (x opacity), which
 //                               enters the 2D covariance's gradient beside the conic's; comp is recomputed, not read.
+//   v3a_gs_project_backward_cam the kernel above for the four Gaussian gradients (the same bits), then its CAM instantiation, which
+//                               writes camera partials only: per camera, every lane's 15 terms of dL/d(R, t, campos) go to
+//                               fp64, are summed over the wave (DPP, wave_sum's order) into one partial row [C, n_waves, 15] ->
+//                               gs_cam_finish_kernel, one workgroup per camera: partials in index order, block_sum, ONE rounding to f32.
 // No atomics on floats anywhere: every sum has a fixed order, results are bit-identical run to run.
 #include "common.h"
+#include "fixed_sum.h"
 #include "gs_raster.h"
 #include "../../include/vist3a_hip.h"
 
@@ -289,10 +295,12 @@ struct ProjGeo {  // what the forward derives from the call's constants
 // s = this Gaussian's SH row, vm2 / vcon / vcol = the entry's incoming gradients.  Adds into vm[3], vS[6] (symmetric dL/dS of the
 // full matrix, same packing) and dsh[3 * NB] (basis-major: dsh[3 k + channel]).  AA (antialiased mode): vop_eff = the entry's
 // dL/d(effective opacity), opac = the Gaussian's opacity; returns comp, and dL/dcomp = vop_eff * opac joins the conic's dL/dQ.
-template <int DEG, bool AA>
+// CAM: also WRITES the entry's 15 camera terms to cam: [0..8] dL/dR (row-major) = v_c m^T + 2 W R S, [9..11] dL/dt = v_c (the
+// camera-space mean gradient), [12..14] dL/dcampos = -dL/dd (the SH view direction; 0 where |d| < 1e-20, as the means' term).
+template <int DEG, bool AA, bool CAM = false>
 __host__ __device__ __forceinline__ float proj_bwd_entry(const ProjGeo& q, const float* m, const float* sw, const float* s, int sh_layout,
                                                          int sh_k, const float* vm2, const float* vcon, const float* vcol, float vop_eff,
-                                                         float opac, float* vm, float* vS, float* dsh) {
+                                                         float opac, float* vm, float* vS, float* dsh, float* cam = nullptr) {
   constexpr int NB = (DEG + 1) * (DEG + 1);
   const float* V = q.V;
   const float R00 = V[0], R01 = V[1], R02 = V[2], R10 = V[4], R11 = V[5], R12 = V[6], R20 = V[8], R21 = V[9], R22 = V[10];
@@ -343,6 +351,22 @@ __host__ __device__ __forceinline__ float proj_bwd_entry(const ProjGeo& q, const
   if (yz >= -lyn && yz <= lyp) { vy += rz * z * vty; vrz += y * z * vty; }
   vz -= rz2 * vrz;
   vm[0] += R00 * vx + R10 * vy + R20 * vz; vm[1] += R01 * vx + R11 * vy + R21 * vz; vm[2] += R02 * vx + R12 * vy + R22 * vz;
+  if constexpr (CAM) {  // mc = R m + t,  Cc = R S R^T:  dL/dt = v_c,  dL/dR = v_c m^T + 2 (W R) S  (b = W R from above)
+    const float s00 = sw[0], s01 = sw[1], s02 = sw[2], s11 = sw[3], s12 = sw[4], s22 = sw[5];
+    const float cx = vx, cy = vy, cz = vz, ox = mx, oy = my, oz = mz;
+    const float d00 = b00, d01 = b01, d02 = b02, d10 = b10, d11 = b11, d12 = b12;
+    const float d20 = b20, d21 = b21, d22 = b22;
+    cam[0] = cx * ox + 2.f * (d00 * s00 + d01 * s01 + d02 * s02);
+    cam[1] = cx * oy + 2.f * (d00 * s01 + d01 * s11 + d02 * s12);
+    cam[2] = cx * oz + 2.f * (d00 * s02 + d01 * s12 + d02 * s22);
+    cam[3] = cy * ox + 2.f * (d10 * s00 + d11 * s01 + d12 * s02);
+    cam[4] = cy * oy + 2.f * (d10 * s01 + d11 * s11 + d12 * s12);
+    cam[5] = cy * oz + 2.f * (d10 * s02 + d11 * s12 + d12 * s22);
+    cam[6] = cz * ox + 2.f * (d20 * s00 + d21 * s01 + d22 * s02);
+    cam[7] = cz * oy + 2.f * (d20 * s01 + d21 * s11 + d22 * s12);
+    cam[8] = cz * oz + 2.f * (d20 * s02 + d21 * s12 + d22 * s22);
+    cam[9] = cx; cam[10] = cy; cam[11] = cz;
+  }
   // SH colour: clamp_min(c + 0.5, 0) mask, coefficients, and the view direction
   const float dx = mx - q.campos[0], dy = my - q.campos[1], dz = mz - q.campos[2];
   const float nrm = sqrtf(dx * dx + dy * dy + dz * dz);
@@ -363,6 +387,13 @@ __host__ __device__ __forceinline__ float proj_bwd_entry(const ProjGeo& q, const
   sh_eval_bwd<DEG>(ux, uy, uz, gk, vux, vuy, vuz);
   const float dot = ux * vux + uy * vuy + uz * vuz;  // u = d / |d|:  dL/dd = (v - u (u . v)) / |d|
   if (nrm >= 1e-20f) { vm[0] += (vux - ux * dot) * inv; vm[1] += (vuy - uy * dot) * inv; vm[2] += (vuz - uz * dot) * inv; }
+  if constexpr (CAM) {  // d = m - campos
+    const bool far = nrm >= 1e-20f;
+    const float ax = vux, ay = vuy, az = vuz, ex = ux, ey = uy, ez = uz;
+    const float od = dot, oi = inv;
+    cam[12] = far ? -((ax - ex * od) * oi) : 0.f; cam[13] = far ? -((ay - ey * od) * oi) : 0.f;
+    cam[14] = far ? -((az - ez * od) * oi) : 0.f;
+  }
   return comp;
 }
 
@@ -377,10 +408,42 @@ struct ProjBwdP {
   float* d_means; float* d_covars; float* d_sh; float* d_opacities;
 };
 
+constexpr int NCAM = 15;  // camera terms of an entry: dL/dR (9), dL/dt (3), dL/dcampos (3)
+
+struct ProjBwdCamP : ProjBwdP {
+  double* part;  // out [C, n_waves, NCAM]: the waves' fp64 sums, n_waves = the grid
+};
+
+// v from the lane the DPP control names, +0.0 where it names none (or the row is masked off): dpp_f32 on the two halves of a double
+template <int CTRL, int ROW_MASK = 0xF>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const unsigned long long b = __builtin_bit_cast(unsigned long long, v);
+  const unsigned int lo = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)b, CTRL, ROW_MASK, 0xF, false);
+  const unsigned int hi = (unsigned int)__builtin_amdgcn_update_dpp(0, (int)(unsigned int)(b >> 32), CTRL, ROW_MASK, 0xF, false);
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
+// wave_sum_lane63 in fp64, the same order: quads, half rows, rows, rows 0+1 / 2+3, halves.  All 64 lanes must be active.
+__device__ __forceinline__ double wave_sum_lane63_f64(double v) {
+  v += dpp_f64<0xB1>(v);
+  v += dpp_f64<0x4E>(v);
+  v += dpp_f64<0x141>(v);
+  v += dpp_f64<0x140>(v);
+  v += dpp_f64<0x142, 0xA>(v);
+  v += dpp_f64<0x143, 0xC>(v);
+  return v;
+}
+
 // One wave = 64 consecutive Gaussians, cameras in index order.  LDS: the SH rows of the 64 Gaussians (as the forward stages them),
 // overwritten at the end by their gradient rows for a coalesced store.
-template <int DEG, bool AA>
-__global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
+// CAM (v3a_gs_project_backward_cam) is a body of its own, so that the other instantiations hold no trace of it (see project_entry
+// in gs_raster.h for why): no lane leaves the camera loop - a culled entry and a lane past U carry 15 exact zeros - because the
+// wave sums each camera's terms one at a time (fp32 -> fp64 is exact) and lane 63 stores the partial row.  It writes the camera
+// partials ONLY: its own sums for means / covars / sh come out of hipcc with other fma contractions than the plain instantiation's
+// (measured: last bits differ), so the entry point gets the four Gaussian gradients from the plain kernel, bit for bit, and this
+// one drops them (dead code; the SH accumulators go, and with them most of the registers).
+template <int DEG, bool AA, bool CAM = false>
+__global__ __launch_bounds__(64) void gs_project_bwd_kernel(std::conditional_t<CAM, ProjBwdCamP, ProjBwdP> p) {
   extern __shared__ float s_sh[];
   constexpr int NB = (DEG + 1) * (DEG + 1);
   const int lane = threadIdx.x;
@@ -392,7 +455,41 @@ __global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
   stage_sh_rows(s_sh, p.sh + (long)g0 * row, total, lane);
   __syncthreads();
   float* s = s_sh + lane * row;
-  if (g < p.U) {
+  if constexpr (CAM) {
+    const bool live = g < p.U;
+    const int gl = live ? g : p.U - 1;  // a lane past U reads the last Gaussian's scalars and uses none of them
+    float vm[3] = {0.f, 0.f, 0.f}, vS[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};   // proj_bwd_entry's Gaussian sums: unused here, dead code
+    float dsh[3 * NB];
+#pragma unroll
+    for (int i = 0; i < 3 * NB; ++i) dsh[i] = 0.f;
+    const float m[3] = {p.means[3L * gl], p.means[3L * gl + 1], p.means[3L * gl + 2]};
+    const float* cv = p.covars + 9L * gl;
+    const float sw[6] = {cv[0], cv[1], cv[2], cv[4], cv[5], cv[8]};
+    float opac = 0.f;
+    if constexpr (AA) opac = p.opac[gl];
+    for (int c = 0; c < p.C; ++c) {
+      const long o = (long)c * p.U + gl;
+      float cam[NCAM];
+#pragma unroll
+      for (int k = 0; k < NCAM; ++k) cam[k] = 0.f;
+      if (live && p.radii[o] > 0) {
+        const ProjGeo q = {p.viewmat + 16 * c, p.K + 9 * c, p.campos + 3 * c, (float)p.W, (float)p.H, p.eps2d};
+        const float vm2[2] = {p.d_means2d[2 * o], p.d_means2d[2 * o + 1]};
+        const float vcon[3] = {p.d_conics[3 * o], p.d_conics[3 * o + 1], p.d_conics[3 * o + 2]};
+        const f32x4 vc4 = *(const f32x4*)(p.d_colors + 4 * o);
+        const float vcol[4] = {vc4[0], vc4[1], vc4[2], vc4[3]};
+        const float vo = p.d_opac[o];
+        proj_bwd_entry<DEG, AA, true>(q, m, sw, s, p.sh_layout, p.sh_k, vm2, vcon, vcol, vo, opac, vm, vS, dsh, cam);
+      }
+      double* dst = p.part + ((size_t)c * gridDim.x + blockIdx.x) * NCAM;
+#pragma unroll
+      for (int k = 0; k < NCAM; ++k) {
+        const double t = wave_sum_lane63_f64((double)cam[k]);
+        if (lane == 63) dst[k] = t;
+      }
+    }
+    return;  // the Gaussian gradients are the other instantiation's: nothing of d_means / d_covars / d_sh / d_opacities is written here
+  } else if (g < p.U) {
     float vm[3] = {0.f, 0.f, 0.f}, vS[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, vop = 0.f;
     float dsh[3 * NB];
 #pragma unroll
@@ -435,6 +532,36 @@ __global__ __launch_bounds__(64) void gs_project_bwd_kernel(ProjBwdP p) {
   float* dst = p.d_sh + (long)g0 * row;
   for (int i = lane; i < total; i += 64) dst[i] = s_sh[i];
 }
+
+struct CamFinishP { const double* part; int n_waves; float* d_viewmat; float* d_campos; };
+
+// One workgroup per camera: lane t adds the partial rows t, t + 256, ... in index order, block_sum over the lanes, one rounding.
+// Every element of d_viewmat [C,4,4] (bottom row: zeros) and d_campos [C,3] is written, nothing is memset.
+__global__ __launch_bounds__(256) void gs_cam_finish_kernel(CamFinishP p) {
+  __shared__ double red[256];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const double* src = p.part + (size_t)c * p.n_waves * NCAM;
+  double acc[NCAM];
+#pragma unroll
+  for (int k = 0; k < NCAM; ++k) acc[k] = 0.0;
+  for (int w = tid; w < p.n_waves; w += 256) {
+#pragma unroll
+    for (int k = 0; k < NCAM; ++k) acc[k] += src[(size_t)w * NCAM + k];
+  }
+  float* vmat = p.d_viewmat + 16 * c;
+#pragma unroll
+  for (int k = 0; k < NCAM; ++k) {
+    const float t = (float)block_sum<256>(acc[k], red);
+    if (tid == 0) {
+      if (k < 9) vmat[4 * (k / 3) + k % 3] = t;        // dL/dR
+      else if (k < 12) vmat[4 * (k - 9) + 3] = t;      // dL/dt
+      else p.d_campos[3 * c + (k - 12)] = t;
+    }
+  }
+  if (tid < 4) vmat[12 + tid] = 0.f;
+}
+
+inline long cam_waves(long U) { return (U + 63) / 64; }
 
 }  // namespace
 
@@ -482,5 +609,34 @@ extern "C" int v3a_gs_project_backward(const v3a_gs_project_backward_args* a, vo
   dispatch_sh_degree_mode(a->sh_degree, a->rasterize_mode, [&](auto d, auto aa) {
     launch_sh_waves(gs_project_bwd_kernel<decltype(d)::value, decltype(aa)::value>, p, (hipStream_t)stream);
   });
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}
+
+extern "C" long v3a_gs_project_backward_cam_workspace_bytes(long U, int C) {
+  if (U < 0 || C <= 0 || U >= (1L << 31)) return V3A_ERR_SHAPE;
+  return (long)(sizeof(double) * NCAM * (size_t)cam_waves(U) * (size_t)C);
+}
+
+extern "C" int v3a_gs_project_backward_cam(const v3a_gs_project_backward_args* a, float* d_viewmat, float* d_campos, void* workspace,
+                                           long workspace_bytes, void* stream) {
+  if (!a || !a->means || !a->covars || !a->sh || !a->viewmat || !a->campos || !a->K || !a->radii || !a->d_means2d || !a->d_conics ||
+      !a->d_colors || !a->d_opacity_partial || !a->d_means || !a->d_covars || !a->d_sh || !a->d_opacities || !d_viewmat || !d_campos ||
+      !workspace)
+    return V3A_ERR_ARG;
+  if (const int rc = check_sh_args(*a)) return rc;
+  if (a->rasterize_mode == 1 && !a->opacities) return V3A_ERR_ARG;
+  if (((uintptr_t)workspace & 7) != 0) return V3A_ERR_ARG;
+  if (workspace_bytes < v3a_gs_project_backward_cam_workspace_bytes(a->U, a->C)) return V3A_ERR_WORKSPACE;
+  ProjBwdCamP p = {{a->means, a->covars, a->sh, a->viewmat, a->campos, a->K, a->sh_layout, a->sh_k, (int)a->U, a->C, a->width, a->height,
+                    a->eps2d, a->radii, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial, a->opacities, a->d_means, a->d_covars,
+                    a->d_sh, a->d_opacities},
+                   (double*)workspace};
+  if (a->U > 0)
+    dispatch_sh_degree_mode(a->sh_degree, a->rasterize_mode, [&](auto d, auto aa) {
+      launch_sh_waves(gs_project_bwd_kernel<decltype(d)::value, decltype(aa)::value>, static_cast<const ProjBwdP&>(p), (hipStream_t)stream);
+      launch_sh_waves(gs_project_bwd_kernel<decltype(d)::value, decltype(aa)::value, true>, p, (hipStream_t)stream);
+    });
+  const CamFinishP f = {p.part, (int)cam_waves(a->U), d_viewmat, d_campos};  // U == 0: no partials, exact zeros
+  hipLaunchKernelGGL(gs_cam_finish_kernel, dim3((unsigned)a->C), dim3(256), 0, (hipStream_t)stream, f);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

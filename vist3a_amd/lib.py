@@ -372,6 +372,8 @@ SYMBOLS = {
     "v3a_gs_rasterize_backward_workspace_bytes": (C.c_long, [C.c_long, C.c_int, C.c_int, C.c_int, C.c_long]),
     "v3a_gs_rasterize_backward": (C.c_int, [C.POINTER(GsRasterizeBackwardArgs), C.c_void_p]),
     "v3a_gs_project_backward": (C.c_int, [C.POINTER(GsProjectBackwardArgs), C.c_void_p]),
+    "v3a_gs_project_backward_cam_workspace_bytes": (C.c_long, [C.c_long, C.c_int]),
+    "v3a_gs_project_backward_cam": (C.c_int, [C.POINTER(GsProjectBackwardArgs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
     "v3a_softmax_rows":(C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "v3a_image_metrics_workspace_bytes": (C.c_long, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "v3a_image_metrics": (C.c_int, [C.POINTER(ImageMetricsArgs), C.c_void_p]),
@@ -404,6 +406,8 @@ SYMBOLS = {
     "v3a_splat_activate": (C.c_int, [C.c_void_p] * 3 + [C.c_long] + [C.c_void_p] * 3),
     "v3a_splat_activate_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),
     "v3a_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
+    "v3a_camera_adjust": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
+    "v3a_camera_adjust_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2),
     "v3a_splat_reg_workspace_bytes": (C.c_long, [C.c_long]),
     "v3a_splat_reg": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
     "v3a_splat_reg_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 4),
@@ -418,7 +422,7 @@ SYMBOLS = {
 }
 
 _lib = None
-EXPECTED_ABI = 31   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 32   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

@@ -1150,10 +1150,12 @@ def gs_rasterize_backward(proj: dict, opacities: torch.Tensor, width: int, heigh
 def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, viewmat: torch.Tensor, campos: torch.Tensor,
                         K: torch.Tensor, width: int, height: int, radii: torch.Tensor, entry_grads: dict, *, sh_degree: int = 4,
                         sh_layout: int = 1, eps2d: float = 0.3, rasterize_mode: str = "classic",
-                        opacities: Optional[torch.Tensor] = None):
+                        opacities: Optional[torch.Tensor] = None, camera_grad: bool = False):
     """Backward of gs_project: the entry gradients of gs_rasterize_backward (or any dict with d_means2d, d_conics, d_colors,
     d_opacity) -> (d_means [U,3], d_covars [U,3,3], d_sh like sh, d_opacities [U]), summed over the cameras in index order.
-    Cameras are constants: there is no gradient for viewmat / campos / K.  rasterize_mode="antialiased" needs `opacities` [U]:
+    Cameras are constants unless camera_grad=True, which calls v3a_gs_project_backward_cam and returns two more tensors,
+    d_viewmat (shaped like viewmat, bottom row zero) and d_campos (like campos); the first four are the same bits either way.
+    There is no gradient for K.  rasterize_mode="antialiased" needs `opacities` [U]:
     d_opacity is then taken as the gradient of opacity * compensation, and the compensation's share reaches means and covars."""
     mode = _gs_mode(rasterize_mode)
     Cn, U, sh_k = _gs_scene_args(means, covars, sh, viewmat, campos, K, sh_layout)
@@ -1173,6 +1175,14 @@ def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Ten
                                 width, height, eps2d, _ptr(radii), _ptr(entry_grads["d_means2d"]), _ptr(entry_grads["d_conics"]),
                                 _ptr(entry_grads["d_colors"]), _ptr(entry_grads["d_opacity"]), _ptr(d_means), _ptr(d_covars), _ptr(d_sh),
                                 _ptr(d_op), mode, _ptr(opacities) if mode else None)
+    if camera_grad:
+        lib = L.load()
+        ws, ws_bytes = _workspace(lib.v3a_gs_project_backward_cam_workspace_bytes(U, Cn),
+                                  f"v3a_gs_project_backward_cam_workspace_bytes (U = {U}, C = {Cn})", means.device)
+        d_view, d_campos = torch.empty_like(viewmat), torch.empty_like(campos)
+        L.check(lib.v3a_gs_project_backward_cam(C.byref(a), _ptr(d_view), _ptr(d_campos), _ptr(ws), ws_bytes, _stream()),
+                "v3a_gs_project_backward_cam")
+        return d_means, d_covars, d_sh, d_op, d_view, d_campos
     L.check(L.load().v3a_gs_project_backward(C.byref(a), _stream()), "v3a_gs_project_backward")
     return d_means, d_covars, d_sh, d_op
 
@@ -1180,7 +1190,7 @@ def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Ten
 class _GsRender(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, covars, sh, opacities, viewmat, campos, K, width, height, sh_degree, sh_layout, background, clamp_rgb,
-                workspace, n_isect_out, rasterize_mode):
+                workspace, n_isect_out, rasterize_mode, camera_grad):
         pr = gs_project(means, covars, sh, viewmat, campos, K, width, height, sh_degree=sh_degree, sh_layout=sh_layout,
                         rasterize_mode=rasterize_mode)
         r = gs_rasterize(pr, opacities, width, height, background=background, clamp_rgb=clamp_rgb, workspace=workspace, return_order=True)
@@ -1189,6 +1199,7 @@ class _GsRender(torch.autograd.Function):
         ctx.save_for_backward(means, covars, sh, opacities, viewmat, campos, K, pr["radii"], pr["means2d"], pr["conics"], pr["colors"],
                               r["tile_offsets"], r["flatten_ids"].contiguous(), *([pr["compensations"]] if "compensations" in pr else []))
         ctx.cfg = (width, height, sh_degree, sh_layout, background, clamp_rgb, workspace, rasterize_mode)
+        ctx.camera_grad = camera_grad
         return r["color"], r["depth"], r["alpha"]
 
     @staticmethod
@@ -1205,29 +1216,81 @@ class _GsRender(torch.autograd.Function):
             pr["compensations"] = comp[0]
         eg = gs_rasterize_backward(pr, opacities, width, height, offs, ids, z(d_color, 3), z(d_depth), z(d_alpha), background=background,
                                    clamp_rgb=clamp_rgb, workspace=workspace.bwd if workspace is not None else None)
+        if ctx.camera_grad:
+            d_means, d_covars, d_sh, d_op, d_view, d_campos = gs_project_backward(
+                means, covars, sh, viewmat, campos, K, width, height, radii, eg, sh_degree=sh_degree, sh_layout=sh_layout,
+                rasterize_mode=rasterize_mode, opacities=opacities if comp else None, camera_grad=True)
+            return (d_means, d_covars, d_sh, d_op, d_view, d_campos) + (None,) * 11
         d_means, d_covars, d_sh, d_op = gs_project_backward(means, covars, sh, viewmat, campos, K, width, height, radii, eg,
                                                             sh_degree=sh_degree, sh_layout=sh_layout, rasterize_mode=rasterize_mode,
                                                             opacities=opacities if comp else None)
-        return (d_means, d_covars, d_sh, d_op) + (None,) * 12
+        return (d_means, d_covars, d_sh, d_op) + (None,) * 13
 
 
 def gs_render(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, opacities: torch.Tensor, viewmat: torch.Tensor,
               campos: torch.Tensor, K: torch.Tensor, width: int, height: int, *, sh_degree: int = 4, sh_layout: int = 1,
               background: Optional[torch.Tensor] = None, clamp_rgb: bool = True, workspace: Optional[GsWorkspace] = None,
-              n_isect_out: Optional[list] = None, rasterize_mode: str = "classic"):
+              n_isect_out: Optional[list] = None, rasterize_mode: str = "classic", camera_grad: bool = False):
     """Differentiable gs_project + gs_rasterize for C cameras (viewmat [C,4,4], campos [C,3], K [C,3,3]) ->
     (color [C,H,W,3], depth [C,H,W], alpha [C,H,W]) with gradients to means, covars, sh and opacities through the HIP backward
-    kernels (csrc/raster_bwd.hip).  The forward values are gs_rasterize's, bit for bit.  Cameras are constants (gsplat's optional
-    pose gradients are not implemented): viewmat / campos / K that require grad are refused.  First-order only.
+    kernels (csrc/raster_bwd.hip).  The forward values are gs_rasterize's, bit for bit.  By default cameras are constants:
+    viewmat / campos / K that require grad are refused.  camera_grad=True (gsplat's optional pose gradients) accepts a viewmat /
+    campos that requires grad and hands it its gradient (v3a_gs_project_backward_cam; the other four gradients keep their bits);
+    viewmat and campos are independent inputs here, so a pose reaches both through whatever computed them (ops.camera_adjust).
+    K that requires grad is refused either way.  First-order only.
     rasterize_mode="antialiased": gsplat's mode of that name, forward and backward (every entry's opacity times its compensation)."""
     _gs_mode(rasterize_mode)
     for t, n in ((viewmat, "viewmat"), (campos, "campos"), (K, "K")):
-        if t.requires_grad:
-            raise NotImplementedError(f"gs_render: no gradient for {n} (camera pose / intrinsics gradients are not implemented)")
+        if t.requires_grad and not (camera_grad and n != "K"):
+            raise NotImplementedError(f"gs_render: no gradient for {n} (camera pose / intrinsics gradients are not implemented)"
+                                      if not camera_grad else "gs_render: no gradient for K (intrinsics are not optimised)")
     if viewmat.dim() != 3:
         raise ValueError("gs_render: viewmat [C,4,4], campos [C,3], K [C,3,3] required")
     return _GsRender.apply(means, covars, sh, opacities, viewmat, campos, K, width, height, sh_degree, sh_layout, background,
-                           clamp_rgb, workspace, n_isect_out, rasterize_mode)
+                           clamp_rgb, workspace, n_isect_out, rasterize_mode, bool(camera_grad))
+
+
+class _CameraAdjust(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, w2c_base, c2w_base, deltas):
+        V = deltas.shape[0]
+        viewmat = torch.empty(V, 4, 4, device=deltas.device, dtype=f32)
+        campos = torch.empty(V, 3, device=deltas.device, dtype=f32)
+        L.check(L.load().v3a_camera_adjust(_ptr(w2c_base), _ptr(c2w_base), _ptr(deltas), V, _ptr(viewmat), _ptr(campos), _stream()),
+                "v3a_camera_adjust")
+        ctx.save_for_backward(w2c_base, c2w_base, deltas)
+        return viewmat, campos
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_viewmat, d_campos):
+        w2c_base, c2w_base, deltas = ctx.saved_tensors
+        V = deltas.shape[0]
+        z = lambda g, *s: torch.zeros(V, *s, device=deltas.device, dtype=f32) if g is None else g.float().contiguous()
+        d_viewmat, d_campos = z(d_viewmat, 4, 4), z(d_campos, 3)
+        d_deltas = torch.empty_like(deltas)
+        L.check(L.load().v3a_camera_adjust_backward(_ptr(w2c_base), _ptr(c2w_base), _ptr(deltas), _ptr(d_viewmat), _ptr(d_campos), V,
+                                                    _ptr(d_deltas), _stream()), "v3a_camera_adjust_backward")
+        return None, None, d_deltas
+
+
+def camera_adjust(w2c_base: torch.Tensor, c2w_base: torch.Tensor, deltas: torch.Tensor):
+    """The pose optimiser's parametrisation (the reference's CameraOptModule): base cameras w2c_base / c2w_base f32 [V,4,4] (each
+    other's inverse, computed once on the host) and deltas f32 [V,9] = (translation[3], 6D rotation[6]) -> (viewmat [V,4,4],
+    campos [V,3]) of the adjusted cameras c2w_base [Rd | dx], as gs_render takes them, with the gradient to `deltas` (HIP, closed
+    form in both directions).  Zero deltas return the base matrices bit for bit.  The bases are constants: refused if they require
+    grad."""
+    for t, n, shape in ((w2c_base, "w2c_base", (4, 4)), (c2w_base, "c2w_base", (4, 4)), (deltas, "deltas", (9,))):
+        if t.dtype != f32 or not t.is_cuda or not t.is_contiguous() or t.dim() != len(shape) + 1 or tuple(t.shape[1:]) != shape:
+            raise ValueError(f"camera_adjust: {n} must be a contiguous fp32 device tensor [V,{','.join(map(str, shape))}], got {t.dtype} "
+                             f"{tuple(t.shape)}")
+    if not (w2c_base.shape[0] == c2w_base.shape[0] == deltas.shape[0]) or deltas.shape[0] < 1:
+        raise ValueError(f"camera_adjust: w2c_base, c2w_base and deltas disagree on the number of cameras: {w2c_base.shape[0]}, "
+                         f"{c2w_base.shape[0]}, {deltas.shape[0]}")
+    for t, n in ((w2c_base, "w2c_base"), (c2w_base, "c2w_base")):
+        if t.requires_grad:
+            raise NotImplementedError(f"camera_adjust: no gradient for {n} (the base cameras are constants; the deltas train)")
+    return _CameraAdjust.apply(w2c_base, c2w_base, deltas)
 
 
 def image_metrics(a_u8: torch.Tensor, b_u8: torch.Tensor):

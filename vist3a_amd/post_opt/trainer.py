@@ -27,6 +27,13 @@ cfg.mcmc_refine_every steps, Gaussians at or below cfg.mcmc_min_opacity are relo
 opacity-gated, covariance-shaped noise to the means.  All of it is csrc/mcmc.hip with counter-based random numbers keyed by
 cfg.seed and the step, so two runs are bit-identical; nothing is read back.  With the default "none" the loop is as it was.
 
+cfg.pose_opt is the reference's camera pose optimisation (:335-339, :653-663, :824-829, :891-892, :1120-1122; utils.py:12-48
+CameraOptModule): 9 deltas per training view (translation + 6D rotation, zero at the start) adjust the view's camera through
+ops.camera_adjust, the render takes ops.gs_render(camera_grad=True), and the deltas train with an Adam of their own (weight decay
+pose_opt_reg, torch's default eps 1e-8, rate decaying to 1 % over max_steps).  The reference runs it BY DEFAULT (pose_opt = True);
+here it is off by default so that no existing call changes - a stated deviation.  The deltas stay in
+`splats["pose_deltas"]`; adjusted_extrinsics turns them into cameras.
+
 The harmonics stay ONE [U,3,K] tensor: the reference's sh0 / shN optimisers (rates lr_sh and lr_sh / 20) are one ops.adam_step with
 a period of K, which is the same arithmetic because Adam is elementwise."""
 from __future__ import annotations
@@ -76,6 +83,9 @@ class PostOptConfig:
     mcmc_refine_every: int = 100
     mcmc_min_opacity: float = 0.005  # at or below it a Gaussian is dead: relocated at the next refine
     test_every: int = 0              # k > 0: the views with index % k == 0 are held out of the loop (the reference's dataset split, test_every)
+    pose_opt: bool = False           # :335-336; True in the reference - off here so that existing calls keep their bits (a stated deviation)
+    pose_opt_lr: float = 1e-5        # :337
+    pose_opt_reg: float = 1e-6       # :338: the pose Adam's weight decay
     # ours
     params: Tuple[str, ...] = ("means", "scales", "quats", "opacities", "sh0", "shN")
     seed: int = 0
@@ -110,6 +120,17 @@ class PostOptConfig:
         if isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 2 ** 64:
             raise ValueError(f"PostOptConfig.seed keys the strategy's random numbers: an integer in [0, 2^64), got {self.seed!r}")
 
+    def check_pose(self) -> None:
+        if not isinstance(self.pose_opt, bool):
+            raise ValueError(f"PostOptConfig.pose_opt must be a bool, got {self.pose_opt!r}")
+        if not self.pose_opt:
+            return
+        if not self.pose_opt_lr > 0 or not self.pose_opt_reg >= 0:
+            raise ValueError(f"PostOptConfig.pose_opt_lr must be positive and pose_opt_reg non-negative, got {self.pose_opt_lr!r} and "
+                             f"{self.pose_opt_reg!r}")
+        if not isinstance(self.max_steps, int) or self.max_steps < 1:
+            raise ValueError(f"PostOptConfig.max_steps must be a positive integer (the pose rate decays over it), got {self.max_steps!r}")
+
     def check_bilagrid(self) -> None:
         if not self.use_bilateral_grid:
             return
@@ -128,6 +149,11 @@ def bilagrid_learning_rate(cfg: PostOptConfig, s: int) -> float:
     warmup), ExponentialLR(0.01 ** (1 / max_steps))) (:831-846)."""
     w = cfg.bilagrid_warmup_steps
     return cfg.bilagrid_lr * (0.01 + 0.99 * min(s, w) / w) * (0.01 ** (s / cfg.max_steps))
+
+
+def pose_learning_rate(cfg: PostOptConfig, s: int) -> float:
+    """The pose Adam's rate at the step with `s` earlier steps: ExponentialLR(0.01 ** (1 / max_steps)) in closed form (:824-829)."""
+    return cfg.pose_opt_lr * (0.01 ** (s / cfg.max_steps))
 
 
 def view_order(n_views: int, steps: int, seed: int) -> list:
@@ -255,6 +281,55 @@ def add_bilateral_grids(splats: dict, cfg: PostOptConfig, n_views: int) -> None:
     splats.update(bil_grids=g, bil_m=torch.zeros_like(g), bil_v=torch.zeros_like(g))
 
 
+def add_pose_deltas(splats: dict, n_views: int) -> None:
+    """splats["pose_deltas"]: zeros f32 [n_views,9], one row per training view, with its Adam moments (CameraOptModule.zero_init)"""
+    d = torch.zeros(n_views, 9, device=splats["params"]["means"].device, dtype=torch.float32)
+    splats.update(pose_deltas=d, pose_m=torch.zeros_like(d), pose_v=torch.zeros_like(d))
+
+
+def _camera_bases(extrinsics, dev):
+    # the full matrices behind _cameras' view and campos (the same two host inversions): what ops.camera_adjust starts from
+    w2c = torch.linalg.inv(extrinsics.detach().float().cpu())
+    c2w = torch.linalg.inv(w2c)
+    return w2c.contiguous().to(dev), c2w.contiguous().to(dev)
+
+
+def pose_transforms(deltas: torch.Tensor) -> torch.Tensor:
+    """deltas [...,9] -> the rigid transforms [Rd | dx] as fp64 [...,4,4] (CameraOptModule's `transform`): a1 = drot[:3] + (1,0,0),
+    a2 = drot[3:] + (0,1,0), Gram-Schmidt with F.normalize's clamp at 1e-12, rows b1, b2, b3 = b1 x b2.  The same few lines stand in
+    tests/pose_opt_oracle.py, which is what is pinned to the reference's module; the tests hold this copy to that one."""
+    d = deltas.detach().double()
+    a1 = d[..., 3:6] + torch.tensor([1.0, 0.0, 0.0], dtype=torch.float64, device=d.device)
+    a2 = d[..., 6:9] + torch.tensor([0.0, 1.0, 0.0], dtype=torch.float64, device=d.device)
+    b1 = a1 / a1.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    u = a2 - (b1 * a2).sum(-1, keepdim=True) * b1
+    b2 = u / u.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    b3 = torch.linalg.cross(b1, b2, dim=-1)
+    T = torch.zeros(*d.shape[:-1], 4, 4, dtype=torch.float64, device=d.device)
+    T[..., :3, :3] = torch.stack((b1, b2, b3), dim=-2)
+    T[..., :3, 3] = d[..., :3]
+    T[..., 3, 3] = 1.0
+    return T
+
+
+def adjusted_extrinsics(extrinsics: torch.Tensor, splats: dict, cfg: PostOptConfig) -> torch.Tensor:
+    """The cameras after pose optimisation: camera-to-world f32 [V,4,4] like `extrinsics`, the training views multiplied by their
+    deltas' transform (c2w [Rd | dx], in fp64, rounded once), held-out views (cfg.test_every) unchanged - the reference does not
+    adjust its validation cameras either.  Without "pose_deltas" in `splats` it is `extrinsics` itself."""
+    if tuple(extrinsics.shape[1:]) != (4, 4) or extrinsics.dim() != 3:
+        raise ValueError(f"adjusted_extrinsics: extrinsics [V,4,4] required, got {tuple(extrinsics.shape)}")
+    out = extrinsics.detach().float().clone()
+    if "pose_deltas" not in splats:
+        return out
+    train = train_views(extrinsics.shape[0], cfg.test_every)
+    deltas = splats["pose_deltas"]
+    if tuple(deltas.shape) != (len(train), 9):
+        raise ValueError(f"splats['pose_deltas'] has shape {tuple(deltas.shape)}, the {len(train)} training views want {(len(train), 9)}")
+    idx = torch.tensor(train, device=out.device)
+    out[idx] = (out[idx].double() @ pose_transforms(deltas).to(out.device)).float()
+    return out
+
+
 def _cameras(extrinsics, intrinsics, W, H, dev):
     # tiny per-camera matrices on the host, exactly as DecoderSplattingCUDA derives them
     w2c = torch.linalg.inv(extrinsics.float().cpu())
@@ -306,14 +381,24 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     the STRATEGY continues where one call would be: its random numbers, the timing of its refines and the grown tensors.  The view
     order and the random backgrounds restart with every call, as they always did, so several calls equal one call only where
     those repeat.  splats["mcmc_counts"], int64 [refines,2] on the device, holds (relocated, added) of every refine;
-    nothing is read back.  The reference pairs the strategy with opacity_reg = scale_reg = 0.01; neither default changes here."""
+    nothing is read back.  The reference pairs the strategy with opacity_reg = scale_reg = 0.01; neither default changes here.
+
+    With cfg.pose_opt, `splats["pose_deltas"]` (zeros f32 [Vt,9] at the start, one row per TRAINING view in their order, moments
+    "pose_m" / "pose_v"; a wrong shape raises) adjusts the step's camera: ops.camera_adjust -> ops.gs_render(camera_grad=True), the
+    deltas being one more leaf of the step's single autograd.grad (the depth term reaches the camera through the rendered depth).
+    Update: ops.adam_step(deltas, grad + cfg.pose_opt_reg * deltas, lr = pose_learning_rate(cfg, steps done), betas (0.9, 0.999),
+    eps 1e-8) - torch.optim.Adam(weight_decay) restated; every row moves each step.  cfg.params may then be empty (a pose-only fit).
+    `extrinsics` that require grad are still refused: the deltas are the loop's own state.  adjusted_extrinsics(extrinsics, splats,
+    cfg) returns the refined cameras; held-out views keep their given poses.  The log has no column of its own for it."""
     cfg = cfg or PostOptConfig()
     cfg.check_bilagrid()
     cfg.check_strategy()
+    cfg.check_pose()
     _single(gaussians)
     for t, n in ((extrinsics, "extrinsics"), (intrinsics, "intrinsics")):
         if t.requires_grad:
-            raise NotImplementedError(f"post_optimize: no gradient for {n} (cameras are constants; pose optimisation is not implemented)")
+            raise NotImplementedError(f"post_optimize: no gradient for {n} (the given cameras are constants; cfg.pose_opt trains pose "
+                                      "deltas of the loop's own)")
     if images.dim() != 4 or images.shape[-1] != 3 or images.dtype != torch.float32:
         raise ValueError(f"images must be float32 [V,H,W,3], got {images.dtype} {tuple(images.shape)}")
     V, H, W, _ = images.shape
@@ -348,10 +433,18 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
         if tuple(splats["bil_grids"].shape) != (Vt, Lz, GY, GX, 12):
             raise ValueError(f"splats['bil_grids'] has shape {tuple(splats['bil_grids'].shape)}, the {Vt} training views and "
                              f"cfg.bilateral_grid_shape want {(Vt, Lz, GY, GX, 12)}")
+    pose = cfg.pose_opt
+    if pose:
+        if "pose_deltas" not in splats:
+            add_pose_deltas(splats, Vt)
+        if tuple(splats["pose_deltas"].shape) != (Vt, 9):
+            raise ValueError(f"splats['pose_deltas'] has shape {tuple(splats['pose_deltas'].shape)}, the {Vt} training views want {(Vt, 9)}")
     dev = p["means"].device
     Ksh = p["sh"].shape[-1]
     sh_degree = isqrt(Ksh) - 1
     view, campos, Kpix = _cameras(extrinsics, intrinsics, W, H, dev)
+    if pose:
+        w2c_base, c2w_base = _camera_bases(extrinsics, dev)
     images = images.contiguous()
     background = torch.zeros(3, device=dev, dtype=torch.float32)
     bkgds = random_backgrounds(steps, cfg.seed).to(dev) if cfg.random_bkgd else None
@@ -365,12 +458,21 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     leaves = [p[n].requires_grad_(True) for n in trained]
     if bil:
         leaves.append(splats["bil_grids"].requires_grad_(True))
+    if pose:   # the last leaf; its gradient is dense [Vt,9] with zero rows for the other views, as nn.Embedding's is
+        leaves.append(splats["pose_deltas"].requires_grad_(True))
     try:
         for i, j in enumerate(train_view_order(V, steps, cfg.seed, cfg.test_every)):
             cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
-            color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
-                                        sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
-                                        clamp_rgb=True, workspace=ws, rasterize_mode=mode)
+            if pose:
+                g_ = grid_of[j]
+                view_j, campos_j = ops.camera_adjust(w2c_base[j:j + 1], c2w_base[j:j + 1], splats["pose_deltas"][g_:g_ + 1])
+                color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view_j, campos_j, Kpix[j:j + 1], W, H,
+                                            sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
+                                            clamp_rgb=True, workspace=ws, rasterize_mode=mode, camera_grad=True)
+            else:
+                color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
+                                            sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
+                                            clamp_rgb=True, workspace=ws, rasterize_mode=mode)
             if bil:
                 color = ops.bilagrid_slice(color, splats["bil_grids"][grid_of[j]:grid_of[j] + 1])
             loss, l1, ssim = ops.photometric_loss(color, images[j:j + 1], cfg.ssim_lambda)
@@ -403,8 +505,12 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
                     ops.adam_step(p[n], g.contiguous(), m[n], v[n], lr=lr, step=t, betas=cfg.betas, eps=cfg.eps,
                                   lr2=lr / 20 if sh else None, period=Ksh if sh and Ksh > 1 else 0)
                 if bil:   # every view's grid moves each step through the TV term, as in the reference
-                    ops.adam_step(splats["bil_grids"], grads[-1].contiguous(), splats["bil_m"], splats["bil_v"],
+                    ops.adam_step(splats["bil_grids"], grads[len(trained)].contiguous(), splats["bil_m"], splats["bil_v"],
                                   lr=bilagrid_learning_rate(cfg, t - 1), step=t, betas=cfg.betas, eps=1e-15, period=0)
+                if pose:  # torch.optim.Adam(weight_decay=reg): the decay joins the gradient; momentum and decay move every row each step
+                    d = splats["pose_deltas"]
+                    ops.adam_step(d, (grads[-1] + cfg.pose_opt_reg * d).contiguous(), splats["pose_m"], splats["pose_v"],
+                                  lr=pose_learning_rate(cfg, t - 1), step=t, betas=(0.9, 0.999), eps=1e-8, period=0)
                 if mcmc:
                     if mcmc_refines_at(cfg, t - 1):
                         mcmc_refine(splats, cfg, t)
@@ -417,4 +523,6 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
             p[n].requires_grad_(False)
         if bil:
             splats["bil_grids"].requires_grad_(False)
+        if pose:
+            splats["pose_deltas"].requires_grad_(False)
     return splats_to_gaussians(splats), log

@@ -68,6 +68,12 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
                    help="the MCMC strategy stops adding Gaussians at N (a scene already above N only relocates)")
     g.add_argument("--post_opt_mcmc_refine", type=str, default="500,25000,100", metavar="START,STOP,EVERY",
                    help="the MCMC strategy refines after the steps i with START < i < STOP and i %% EVERY == 0 (counted from 0)")
+    g.add_argument("--post_opt_pose_opt", action="store_true",
+                   help="refine the predicted camera poses together with the scene (the reference's pose_opt, on by default there): 9 "
+                        "deltas per training view train through the rasteriser's camera gradients; the adjusted cameras are written to "
+                        "post_opt_cameras.json next to gaussians.ply (the videos keep the predicted path)")
+    g.add_argument("--post_opt_pose_lr", type=float, default=None, metavar="X",
+                   help="with --post_opt_pose_opt: the pose optimiser's learning rate (the reference's pose_opt_lr, 1e-5)")
     g.add_argument("--post_opt_eval_every", type=int, default=0, metavar="K",
                    help="hold the views with index %% K == 0 out of the post-optimisation (the reference's test_every) and evaluate them "
                         "before and after it: PSNR, SSIM, the number of Gaussians and a time per image - with --post_opt_bilateral_grid "
