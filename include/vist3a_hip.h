@@ -537,6 +537,8 @@ typedef struct {
   void* workspace; long workspace_bytes;   /* v3a_gs_rasterize_backward_workspace_bytes(U, C, width, height, n_isect); too small: -4 */
   const float* compensations;      /* as v3a_gs_rasterize had it ([C,U] or NULL); d_opacity_partial is then the gradient with
                                       respect to opacities[g] * compensations[c,g] */
+  float* d_means2d_abs;     /* out [C,U,2] or NULL: the sum over pixels of |the pixel's two d_means2d terms| (gsplat's absgrad);
+                               >= |d_means2d| elementwise, 0 for culled entries.  The other four outputs keep their bits. */
 } v3a_gs_rasterize_backward_args;
 long v3a_gs_rasterize_backward_workspace_bytes(long U, int C, int width, int height, long max_isect);
 int v3a_gs_rasterize_backward(const v3a_gs_rasterize_backward_args* a, void* stream);
@@ -830,7 +832,7 @@ int v3a_splat_reg_backward(const float* logits, const float* log_scales, long U,
  * in its `mcmc` configuration).  DESIGN.md section 7f restates the algorithm and is the contract.
  *
  * Random numbers: Philox4x32-10, counter (slot, 0, rng_stream, step), key = seed (low word, high word); no state.  rng_stream 0 is
- * relocation sampling, 1 growth sampling, 2 and 3 the two normal draws of the noise.  A uniform of words (x0, x1) is
+ * relocation sampling, 1 growth sampling, 2 and 3 the two normal draws of the noise, 4 to 7 those of v3a_densify_apply's split children.  A uniform of words (x0, x1) is
  * ((x0 >> 5) 2^26 + (x1 >> 6)) 2^-53 in [0, 1).  v3a_mcmc_philox and v3a_mcmc_uniform run on the HOST (host pointers): the same
  * source as the device code, for known-answer tests.
  * ---------------------------------------------------------------------------------------------- */
@@ -886,6 +888,74 @@ int v3a_mcmc_relocate(const v3a_mcmc_relocate_args* a, void* stream);
  * 44 bytes read and 12 written per Gaussian; the quaternion is one 16-byte load when its pointer is 16-byte aligned. */
 int v3a_mcmc_noise(float* means, const float* log_scales, const float* quats, const float* logits, long U, double scaler,
                    unsigned long long seed, unsigned int step, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Adaptive density control of the post-optimisation loop (csrc/densify.hip; gsplat's DefaultStrategy, which the reference's
+ * `default` configuration is built around, simple_trainer.py:1486-1491).  DESIGN.md section 7f restates it and is the contract.
+ * Shape rules of all four: U < 0 or U >= 2^31 returns V3A_ERR_SHAPE, U == 0 is a no-op.
+ *
+ * Accumulate (every step): for Gaussian g and every camera c in index order with radii[c,g] > 0,
+ *   s += sqrt((gx W/2 C)^2 + (gy H/2 C)^2) in fp64, (gx, gy) = d_means2d[c,g]; n += 1;
+ * then grad2d[g] = (float)(grad2d[g] + s) - one rounding per call - and count[g] += n.  One thread per Gaussian, no scratch. */
+int v3a_densify_accumulate(const float* d_means2d /* [C,U,2] */, const int* radii /* [C,U] */, long U, int C, int width, int height,
+                           float* grad2d /* [U] */, int* count /* [U] */, void* stream);
+
+/* Classify (every refine).  Per parent g, in fp64 on exactly converted f32 values:
+ *   high = grad2d / max(count, 1) > grow_grad2d;  small = max_k exp(ls[g,k]) <= grow_scale3d
+ *   fate = grow ? (high ? (small ? CLONE : SPLIT) : KEEP) : KEEP                       (0 keep, 1 clone, 2 split)
+ *   the rows it leaves are a keep's or clone's copies of the parent (opacity o = sigmoid(logit), scale smax) or a split's two
+ *   children (opacity o, or 1 - sqrt(1 - o) with revised_opacity; scale smax / 1.6); they share one verdict:
+ *   pruned = opacity < prune_opa || (prune_big && scale > prune_scale3d)
+ *   fates[g] = fate | pruned << 2
+ *   counts[0][g] = fate != SPLIT && !pruned   (segment A: the original)
+ *   counts[1][g] = fate == CLONE && !pruned   (segment B: the clone)
+ *   counts[2][g] = fate == SPLIT && !pruned   (segments C and D: the first and the second child)
+ * offsets[s] is the exclusive prefix sum of counts[s] (blocks of 256 parents, then the block totals in order: integers, so the
+ * order cannot change the result) and totals[s] its sum, int64 [3] on the device.  The thresholds come multiplied by the scene
+ * scale.  workspace: v3a_densify_classify_workspace_bytes(U), 8-byte aligned (too small or misaligned: V3A_ERR_WORKSPACE). */
+typedef struct {
+  const float* grad2d; const int* count;          /* [U] */
+  const float* log_scales; const float* logits;   /* [U,3], [U] */
+  long U;
+  double grow_grad2d, grow_scale3d, prune_opa, prune_scale3d;
+  int grow, prune_big, revised_opacity;
+  unsigned char* fates;   /* out [U] */
+  int* counts;            /* out [3,U] */
+  int* offsets;           /* out [3,U] */
+  long* totals;           /* out [3], device */
+  void* workspace; long workspace_bytes;
+} v3a_densify_classify_args;
+long v3a_densify_classify_workspace_bytes(long U);   /* V3A_ERR_SHAPE for U < 0 or U >= 2^31 */
+int v3a_densify_classify(const v3a_densify_classify_args* a, void* stream);
+
+/* Apply (every refine): the new tensors of U_out = totals[0] + totals[1] + 2 totals[2] rows, from the old ones and classify's
+ * fates, offsets and totals.  Row order: A surviving non-split originals in index order (row offsets[0][g]), B surviving clones
+ * (totals[0] + offsets[1][g]), C first children (totals[0] + totals[1] + offsets[2][g]), D second children (C's base + totals[2]
+ * + offsets[2][g]).  A rows copy the parent and its moments bit for bit; a B row copies the parent with zero moments; child c of a
+ * split has ls - log 1.6, the parent's logit (or logit(1 - sqrt(1 - o)) with revised_opacity), quats and sh, zero moments and
+ *   means + R (exp(ls) . z),  R = quat_R of csrc/splat_quat.h, z = (z0, z1) of rng_stream 4 + 2c and z0 of rng_stream 5 + 2c of
+ * v3a_mcmc_philox at counter (g, 0, rng_stream, step), key = seed (Box-Muller as for v3a_mcmc_noise); fp64, one rounding per store.
+ * Every element of every new tensor is written exactly once, zeros included; no memset, no atomics.  A row past U_out is not
+ * written.  The harmonics rows move with 16-byte accesses where source and destination share their phase, scalar otherwise.
+ * Old and new tensors must not overlap (V3A_ERR_SHAPE).  U_out == 0 writes nothing. */
+typedef struct {
+  const float *means, *log_scales, *quats, *logits, *sh;            /* old: [U,3] [U,3] [U,4] [U] [U,3,K] */
+  const float *m_means, *m_log_scales, *m_quats, *m_logits, *m_sh;
+  const float *v_means, *v_log_scales, *v_quats, *v_logits, *v_sh;
+  float *new_means, *new_log_scales, *new_quats, *new_logits, *new_sh;   /* new: U_out rows */
+  float *new_m_means, *new_m_log_scales, *new_m_quats, *new_m_logits, *new_m_sh;
+  float *new_v_means, *new_v_log_scales, *new_v_quats, *new_v_logits, *new_v_sh;
+  const unsigned char* fates; const int* offsets; const long* totals;   /* of v3a_densify_classify */
+  long U, U_out;
+  int K;
+  unsigned long long seed; unsigned int step;
+  int revised_opacity;
+} v3a_densify_apply_args;
+int v3a_densify_apply(const v3a_densify_apply_args* a, void* stream);
+
+/* Opacity reset: logit = min(logit, logit(max_opacity)) (fp64 compare, one rounding), m = v = 0, elementwise on [U];
+ * max_opacity in (0, 1) (else V3A_ERR_SHAPE). */
+int v3a_densify_reset_opacity(float* logits, float* m_logits, float* v_logits, long U, double max_opacity, void* stream);
 
 #ifdef __cplusplus
 }

@@ -66,14 +66,16 @@ def build_text_encoder(args, device):
 
 def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False, eval_every=0, lpips=None,
            antialiased=False, random_bkgd=False, opacity_reg=0.0, scale_reg=0.0, mcmc=None, pose_opt=False, pose_lr=None,
-           cameras_out=None):
+           cameras_out=None, densify=None):
     """-> (refined Gaussians, stats or None).  With eval_every = K > 0 the views with index % K == 0 are held out of the loop and
     scored before and after it: stats = {"before": {...}, "after": {...}, "held_out": [...]} (vist3a_amd.post_opt.evaluate_views).
     antialiased / random_bkgd / opacity_reg / scale_reg: the PostOptConfig fields of those names; the evaluation renders in the
     loop's rasterize mode.  mcmc: None, or (cap_max, (start, stop, every)) to run the loop with cfg.strategy = "mcmc"; the refined
     scene then has as many Gaussians as the strategy left it with.  pose_opt / pose_lr: cfg.pose_opt and cfg.pose_opt_lr (None: its
     default) - scene and cameras are refined together, and the dict `cameras_out` (if given) receives "extrinsics" (the adjusted
-    camera-to-world matrix of every view, held-out views as given), "deltas" [Vt,9] and "train_views", as lists."""
+    camera-to-world matrix of every view, held-out views as given), "deltas" [Vt,9] and "train_views", as lists.
+    densify: None, or densify_options' dict of PostOptConfig fields to run the loop with cfg.strategy = "densify" (adaptive density
+    control: clone / split / prune); the refined scene has as many Gaussians as it left."""
     from vist3a_amd import ops
     from vist3a_amd.post_opt import PostOptConfig, adjusted_extrinsics, create_splats, evaluate_views, post_optimize, train_views
     with torch.no_grad():
@@ -97,6 +99,10 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
     if mcmc is not None:
         cfg.strategy, cfg.mcmc_cap_max = "mcmc", int(mcmc[0])
         cfg.mcmc_refine_start_iter, cfg.mcmc_refine_stop_iter, cfg.mcmc_refine_every = (int(x) for x in mcmc[1])
+    if densify is not None:
+        cfg.strategy = "densify"
+        for k, x in densify.items():
+            setattr(cfg, k, x)
     cfg.pose_opt = bool(pose_opt)
     if pose_lr is not None:
         cfg.pose_opt_lr = float(pose_lr)
@@ -139,6 +145,30 @@ def mcmc_options(args):
     return args.post_opt_mcmc_cap_max, refine_at
 
 
+def densify_options(args):
+    """--post_opt_densify* -> None (off) or the PostOptConfig fields of the "densify" strategy for refine()"""
+    if not args.post_opt_densify:
+        return None
+    if args.post_opt_mcmc:
+        raise ValueError("--post_opt_densify and --post_opt_mcmc are two strategies of the post-optimisation: choose one")
+    if args.post_opt_steps <= 0:
+        raise ValueError("--post_opt_densify needs --post_opt_steps > 0 (it is a strategy of the post-optimisation)")
+    try:
+        at = tuple(int(x) for x in args.post_opt_densify_refine.split(","))
+    except ValueError:
+        at = ()
+    if len(at) != 4 or min(at) < 0 or at[2] < 1 or at[3] < 1:
+        raise ValueError("--post_opt_densify_refine wants four integers START,STOP,EVERY,RESET >= 0 with EVERY, RESET >= 1, got "
+                         f"{args.post_opt_densify_refine!r}")
+    if not args.post_opt_densify_grad > 0:
+        raise ValueError("--post_opt_densify_grad must be positive")
+    if args.post_opt_densify_cap_max < 0:
+        raise ValueError("--post_opt_densify_cap_max must be >= 0 (0 = no cap)")
+    return dict(densify_refine_start_iter=at[0], densify_refine_stop_iter=at[1], densify_refine_every=at[2], densify_reset_every=at[3],
+                densify_grow_grad2d=float(args.post_opt_densify_grad), densify_absgrad=bool(args.post_opt_densify_absgrad),
+                densify_cap_max=int(args.post_opt_densify_cap_max))
+
+
 def main(args):
     setup_dist()
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -164,6 +194,7 @@ def main(args):
     if args.post_opt_opacity_reg < 0 or args.post_opt_scale_reg < 0:
         raise ValueError("--post_opt_opacity_reg and --post_opt_scale_reg are weights >= 0")
     mcmc = mcmc_options(args)
+    densify = densify_options(args)
     if (args.post_opt_pose_opt or args.post_opt_pose_lr is not None) and args.post_opt_steps <= 0:
         raise ValueError("--post_opt_pose_opt / --post_opt_pose_lr need --post_opt_steps > 0 (the poses are refined by the post-optimisation)")
     if args.post_opt_pose_lr is not None and not args.post_opt_pose_lr > 0:
@@ -199,7 +230,7 @@ def main(args):
                               args.post_opt_depth_lambda, args.post_opt_bilateral_grid, args.post_opt_eval_every, lpips,
                               antialiased=args.post_opt_antialiased, random_bkgd=args.post_opt_random_bkgd,
                               opacity_reg=args.post_opt_opacity_reg, scale_reg=args.post_opt_scale_reg, mcmc=mcmc,
-                              pose_opt=args.post_opt_pose_opt, pose_lr=args.post_opt_pose_lr, cameras_out=cameras)
+                              pose_opt=args.post_opt_pose_opt, pose_lr=args.post_opt_pose_lr, cameras_out=cameras, densify=densify)
             if stats is not None:
                 (save / "post_opt_stats.json").write_text(json.dumps(stats, indent=1))
             if args.post_opt_pose_opt:   # the refined cameras; the videos below keep the predicted path, as the reference's trajectory does

@@ -16,7 +16,12 @@ With --pose_opt a further JSON line times pose optimisation (cfg.pose_opt) on th
 camera adjusted through ops.camera_adjust and rendered with camera_grad=True (the deltas one more leaf, their Adam included), the
 projection-backward call alone without and with camera gradients (the second is the plain kernel + the CAM kernel + the finish
 kernel: the projection chain runs twice), and the two camera_adjust launches.  The kernels inside the camera-gradient call are
-told apart with a kernel trace of this tool, not here."""
+told apart with a kernel trace of this tool, not here.
+With --densify a further JSON line times the densification strategy (csrc/densify.hip, cfg.strategy = "densify") on the same
+Gaussians: the per-step accumulate launch (28 B per Gaussian and camera) and one refine's entry points - classify (three launches:
+fates and block scans, block prefix, offsets), apply (two launches: the 11-float rows, the harmonics rows) with a third of the scene
+above the gradient threshold, and the opacity reset; the bytes apply moves over its time.  With --absgrad also the rasteriser's
+backward call without and with the absolute-gradient output (the ABS instantiations of its two kernels)."""
 import argparse
 import json
 import math
@@ -38,7 +43,16 @@ def main():
     ap.add_argument("--bilateral_grid", action="store_true")
     ap.add_argument("--mcmc", action="store_true", help="also time the MCMC strategy's noise launch and the pieces of one refine")
     ap.add_argument("--pose_opt", action="store_true", help="also time the step with pose optimisation and the camera-gradient launches")
+    ap.add_argument("--reserve_gb", type=int, default=0, metavar="N",
+                    help="first take one block of N GB from the driver and hand it to torch's cache, before the library is loaded: every "
+                         "buffer is then carved from that block at the same relative place, so that two builds of the library can be "
+                         "compared (the harmonics' Adam launch alone moves by 7 %% with where its four 720 MB buffers lie)")
+    ap.add_argument("--densify", action="store_true", help="also time the densification strategy's accumulate launch and the pieces of one refine")
+    ap.add_argument("--absgrad", action="store_true", help="with --densify: also the rasteriser's backward without and with absgrad")
     a = ap.parse_args()
+    if a.reserve_gb > 0:
+        block = torch.empty(a.reserve_gb << 30, dtype=torch.uint8, device="cuda")
+        del block                                             # back into torch's caching allocator, not to the driver
     from vist3a_amd import ops
     U, W, H = a.gaussians, a.size, a.size
     g = torch.Generator().manual_seed(9)
@@ -126,8 +140,58 @@ def main():
                           color_correct_read_GBps=round(5 * 48 * W * H / f_ms / 1e6, 1), image_mse_ms=round(m_ms, 3))))
     if a.mcmc:
         print(json.dumps(mcmc_times(ops, {k: t.detach() for k, t in p.items()}, m, v, a.warmup, a.iters)))
+    if a.densify:
+        print(json.dumps(densify_times(ops, {k: t.detach() for k, t in p.items()}, m, v, view, campos, K, bg, ws, W, H, a.absgrad, a.warmup, a.iters)))
     if a.pose_opt:
         print(json.dumps(pose_times(ops, p, view, K, target, bg, ws, W, H, "antialiased" if a.antialiased else "classic", a.warmup, a.iters)))
+
+
+def densify_times(ops, p, m, v, view, campos, K, bg, ws, W, H, absgrad, warmup, iters):
+    U = p["means"].shape[0]
+    timed = {}
+
+    def clock(name, fn):
+        ms = []
+        for it in range(warmup + iters):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out = fn(it)
+            e1.record()
+            torch.cuda.synchronize()
+            if it >= warmup:
+                ms.append(e0.elapsed_time(e1))
+        timed[name] = statistics.median(ms)
+        return out
+
+    with torch.no_grad():
+        cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        pr = ops.gs_project(p["means"], cov, p["sh"], view, campos, K, W, H)
+        r = ops.gs_rasterize(pr, op, W, H, background=bg, workspace=ws, return_order=True)
+        back = lambda on: ops.gs_rasterize_backward(pr, op, W, H, r["tile_offsets"], r["flatten_ids"].contiguous(), d_color, zero, zero,
+                                                    background=bg, absgrad=on)
+        d_color, zero = torch.rand(1, H, W, 3, device="cuda"), torch.zeros(1, H, W, device="cuda")
+        eg = back(True)
+        if absgrad:
+            clock("rasterize_backward", lambda it: back(False))
+            clock("rasterize_backward_absgrad", lambda it: back(True))
+        grad2d, count = torch.zeros(U, device="cuda"), torch.zeros(U, device="cuda", dtype=torch.int32)
+        d2 = eg["d_means2d_abs" if absgrad else "d_means2d"]
+        clock("accumulate", lambda it: ops.densify_accumulate(grad2d, count, d2, pr["radii"], W, H))
+        avg = grad2d / count.clamp(min=1)
+        thr = float(avg[count > 0].float().quantile(2.0 / 3.0)) if U <= 16_000_000 else float(avg.mean())
+        kw = dict(grow_grad2d=thr, grow_scale3d=0.02, prune_opa=0.005, prune_scale3d=0.1, prune_big=True)
+        cls = clock("classify", lambda it: ops.densify_classify(grad2d, count, p["scales"], p["opacities"], **kw))
+        totals = cls["totals"].tolist()
+        new = clock("apply", lambda it: ops.densify_apply(cls, p, m, v, seed=1, step=it + 1, totals=totals))
+        lg, lm, lv = p["opacities"].clone(), m["opacities"].clone(), v["opacities"].clone()
+        clock("reset_opacity", lambda it: ops.densify_reset_opacity(lg, lm, lv, 0.01))
+    U_out = new[0]["means"].shape[0]
+    row = 4 * (11 + 3 * p["sh"].shape[-1])                       # bytes of one row of the five parameter tensors
+    # written: params, m and v of every new row; read: params, m and v of an original, the params alone for a clone or a child
+    moved = 3 * row * U_out + row * (3 * totals[0] + totals[1] + 2 * totals[2])
+    return dict(gaussians=U, size=W, visible=int((pr["radii"] > 0).sum()), absgrad=bool(absgrad), grow_grad2d=thr,
+                kept_cloned_split=totals, rows_after=U_out, accumulate_bytes=28 * U, accumulate_GBps=round(28 * U / timed["accumulate"] / 1e6, 1),
+                apply_bytes=moved, apply_GBps=round(moved / timed["apply"] / 1e6, 1), **{k + "_ms": round(x, 4) for k, x in timed.items()})
 
 
 def pose_times(ops, p, view, K, target, bg, ws, W, H, mode, warmup, iters):

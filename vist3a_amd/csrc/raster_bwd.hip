@@ -29,7 +29,7 @@ namespace {
 
 using namespace gs;
 
-constexpr int ROWF = 12;  // floats per row: d_means2d (2) d_conics (3) d_colors (4) d_opacity (1), padded to three 16-byte stores
+constexpr int ROWF = 12;  // floats per row: d_means2d (2) d_conics (3) d_colors (4) d_opacity (1), then |d_means2d| (2) with ABS, else padding: three 16-byte stores
 constexpr int BB = 128;   // Gaussians per backward round (4 waves x BB x 48 B of LDS partials)
 
 __host__ __device__ __forceinline__ float fast_rcp(float x) {
@@ -102,6 +102,8 @@ __device__ __forceinline__ unsigned int row_slot(const BlendBwdP& p, unsigned in
   return slot < p.n_isect ? slot : ~0u;
 }
 
+// ABS: the row's two spare floats carry the sums of |v[0]|, |v[1]| (gsplat's absgrad) through the same DPP, LDS and slot order.
+template <bool ABS>
 __global__ __launch_bounds__(256) void gs_blend_bwd_kernel(BlendBwdP p) {
   __shared__ f32x4 s_g[256 * 3];        // stage_gaussian's records
   __shared__ f32x4 s_part[4][BB][3];    // per wave, per Gaussian of the round: the ten reduced terms
@@ -165,9 +167,11 @@ __global__ __launch_bounds__(256) void gs_blend_bwd_kernel(BlendBwdP p) {
 #pragma unroll
         for (int i = 0; i < 10; ++i) v[i] = 0.f;
         if (valid) blend_bwd_pair(a[0] - px, a[1] - py, c[0], c[1], c[2], a[2], ex, alpha, s_g[3 * k + 2], gr, gT, Tfin, T, S, v);
+        [[maybe_unused]] const float ab0 = fabsf(v[0]), ab1 = fabsf(v[1]);   // this pixel's terms, before the sums
 #pragma unroll
         for (int i = 0; i < 10; ++i) v[i] = wave_sum_lane63(v[i]);
         o0 = f32x4{v[0], v[1], v[2], v[3]}; o1 = f32x4{v[4], v[5], v[6], v[7]}; o2 = f32x4{v[8], v[9], 0.f, 0.f};
+        if constexpr (ABS) { o2[2] = wave_sum_lane63(ab0); o2[3] = wave_sum_lane63(ab1); }
       }
       if (lane == 63) { s_part[wave][k][0] = o0; s_part[wave][k][1] = o1; s_part[wave][k][2] = o2; }
     }
@@ -198,10 +202,11 @@ struct RowSumP {
   const unsigned int* counts; const unsigned int* incl; const float* rows;
   long CU;
   unsigned int n_isect;
-  float* d_means2d; float* d_conics; float* d_colors; float* d_opac;
+  float* d_means2d; float* d_conics; float* d_colors; float* d_opac; float* d_abs;
 };
 
 // one lane per camera-Gaussian entry: its rows in slot order (tile rectangle, row-major)
+template <bool ABS>
 __global__ __launch_bounds__(256) void gs_rowsum_kernel(RowSumP p) {
   const long e = (long)blockIdx.x * 256 + threadIdx.x;
   if (e >= p.CU) return;
@@ -215,6 +220,7 @@ __global__ __launch_bounds__(256) void gs_rowsum_kernel(RowSumP p) {
   p.d_conics[3 * e] = q0[2]; p.d_conics[3 * e + 1] = q0[3]; p.d_conics[3 * e + 2] = q1[0];
   *(f32x4*)(p.d_colors + 4 * e) = f32x4{q1[1], q1[2], q1[3], q2[0]};
   p.d_opac[e] = q2[1];
+  if constexpr (ABS) { p.d_abs[2 * e] = q2[2]; p.d_abs[2 * e + 1] = q2[3]; }
 }
 
 struct BLayout { size_t counts, incl, rows, tmp, tmp_bytes, total; };
@@ -590,9 +596,15 @@ extern "C" int v3a_gs_rasterize_backward(const v3a_gs_rasterize_backward_args* a
   BlendBwdP bp = {a->radii, a->means2d, a->conics, a->colors, a->opacities, a->compensations, a->tile_offsets, a->flatten_ids, counts, incl, a->background,
                   a->d_color, a->d_depth, a->d_alpha, rows, (unsigned int)a->n_isect, (unsigned int)CU, (int)a->U, a->width, a->height,
                   tg.tw, tg.th, tg.ntiles, a->clamp_rgb};
-  if (a->n_isect > 0) hipLaunchKernelGGL(gs_blend_bwd_kernel, dim3((unsigned)(tg.ntiles * a->C)), dim3(256), 0, stream, bp);
-  RowSumP rp = {counts, incl, rows, CU, (unsigned int)a->n_isect, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial};
-  hipLaunchKernelGGL(gs_rowsum_kernel, dim3(gb), dim3(256), 0, stream, rp);
+  const dim3 bgrid((unsigned)(tg.ntiles * a->C));
+  RowSumP rp = {counts, incl, rows, CU, (unsigned int)a->n_isect, a->d_means2d, a->d_conics, a->d_colors, a->d_opacity_partial, a->d_means2d_abs};
+  if (a->d_means2d_abs) {
+    if (a->n_isect > 0) hipLaunchKernelGGL(gs_blend_bwd_kernel<true>, bgrid, dim3(256), 0, stream, bp);
+    hipLaunchKernelGGL(gs_rowsum_kernel<true>, dim3(gb), dim3(256), 0, stream, rp);
+  } else {
+    if (a->n_isect > 0) hipLaunchKernelGGL(gs_blend_bwd_kernel<false>, bgrid, dim3(256), 0, stream, bp);
+    hipLaunchKernelGGL(gs_rowsum_kernel<false>, dim3(gb), dim3(256), 0, stream, rp);
+  }
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 

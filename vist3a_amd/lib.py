@@ -116,6 +116,7 @@ class GsRasterizeBackwardArgs(C.Structure):
         ("d_means2d", C.c_void_p), ("d_conics", C.c_void_p), ("d_colors", C.c_void_p), ("d_opacity_partial", C.c_void_p),
         ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
         ("compensations", C.c_void_p),
+        ("d_means2d_abs", C.c_void_p),
     ]
 
 
@@ -318,6 +319,31 @@ class McmcRelocateArgs(C.Structure):
     ]
 
 
+class DensifyClassifyArgs(C.Structure):
+    _fields_ = [
+        ("grad2d", C.c_void_p), ("count", C.c_void_p), ("log_scales", C.c_void_p), ("logits", C.c_void_p),
+        ("U", C.c_long),
+        ("grow_grad2d", C.c_double), ("grow_scale3d", C.c_double), ("prune_opa", C.c_double), ("prune_scale3d", C.c_double),
+        ("grow", C.c_int), ("prune_big", C.c_int), ("revised_opacity", C.c_int),
+        ("fates", C.c_void_p), ("counts", C.c_void_p), ("offsets", C.c_void_p), ("totals", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_long),
+    ]
+
+
+_DENSIFY_FIELDS = ("means", "log_scales", "quats", "logits", "sh")
+
+
+class DensifyApplyArgs(C.Structure):
+    _fields_ = (
+        [(pre + f, C.c_void_p) for pre in ("", "m_", "v_", "new_", "new_m_", "new_v_") for f in _DENSIFY_FIELDS]
+        + [("fates", C.c_void_p), ("offsets", C.c_void_p), ("totals", C.c_void_p),
+           ("U", C.c_long), ("U_out", C.c_long),
+           ("K", C.c_int),
+           ("seed", C.c_uint64), ("step", C.c_uint32),
+           ("revised_opacity", C.c_int)]
+    )
+
+
 # name -> (restype, argtypes); every symbol include/vist3a_hip.h declares must be listed here
 SYMBOLS = {
     "v3a_abi_version": (C.c_int, []),
@@ -419,10 +445,15 @@ SYMBOLS = {
     "v3a_mcmc_relocate_workspace_bytes": (C.c_long, [C.c_long]),
     "v3a_mcmc_relocate": (C.c_int, [C.POINTER(McmcRelocateArgs), C.c_void_p]),
     "v3a_mcmc_noise": (C.c_int, [C.c_void_p] * 4 + [C.c_long, C.c_double, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "v3a_densify_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "v3a_densify_classify_workspace_bytes": (C.c_long, [C.c_long]),
+    "v3a_densify_classify": (C.c_int, [C.POINTER(DensifyClassifyArgs), C.c_void_p]),
+    "v3a_densify_apply": (C.c_int, [C.POINTER(DensifyApplyArgs), C.c_void_p]),
+    "v3a_densify_reset_opacity": (C.c_int, [C.c_void_p] * 3 + [C.c_long, C.c_double, C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 32   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 33   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

@@ -1105,11 +1105,13 @@ def _gs_f32(t: torch.Tensor, name: str, numel: int) -> None:
 def gs_rasterize_backward(proj: dict, opacities: torch.Tensor, width: int, height: int, tile_offsets: torch.Tensor,
                           flatten_ids: torch.Tensor, d_color: torch.Tensor, d_depth: torch.Tensor, d_alpha: torch.Tensor, *,
                           background: Optional[torch.Tensor] = None, clamp_rgb: bool = True,
-                          workspace: Optional[GsBwdWorkspace] = None):
+                          workspace: Optional[GsBwdWorkspace] = None, absgrad: bool = False):
     """Backward of gs_rasterize: `proj` and (tile_offsets, flatten_ids) as the forward had / returned them (return_order=True),
     d_color [C,H,W,3], d_depth, d_alpha [C,H,W] -> dict(d_means2d [C,U,2], d_conics [C,U,3], d_colors [C,U,4], d_opacity [C,U])
     per camera-Gaussian entry; without the C axis when `proj` came from a single-camera gs_project call.  With compensations in
-    `proj` (antialiased mode) d_opacity is the gradient with respect to the entry's opacities[g] * compensations[c, g]."""
+    `proj` (antialiased mode) d_opacity is the gradient with respect to the entry's opacities[g] * compensations[c, g].
+    absgrad=True adds d_means2d_abs [C,U,2], the sum over pixels of the absolute per-pixel terms of d_means2d (gsplat's absgrad,
+    what the densification strategy may read); the other four are the same bits either way."""
     U, dev = opacities.shape[0], opacities.device
     if U == 0:
         raise ValueError("no Gaussians to draw")
@@ -1139,12 +1141,16 @@ def gs_rasterize_backward(proj: dict, opacities: torch.Tensor, width: int, heigh
     buf = wsp.get(U, Cn, width, height, max(n_isect, 1))
     e = lambda *s: torch.empty(*lead, *s, device=dev, dtype=f32)
     dm2, dcon, dcol, dop = e(U, 2), e(U, 3), e(U, 4), e(U)
+    dabs = e(U, 2) if absgrad else None
     a = L.GsRasterizeBackwardArgs(_ptr(proj["radii"]), _ptr(proj["means2d"]), _ptr(proj["conics"]), _ptr(proj["colors"]), _ptr(opacities),
                                   _ptr(background) if background is not None else None, U, Cn, width, height, int(clamp_rgb),
                                   _ptr(tile_offsets), _ptr(flatten_ids) if n_isect else None, n_isect, _ptr(d_color), _ptr(d_depth),
-                                  _ptr(d_alpha), _ptr(dm2), _ptr(dcon), _ptr(dcol), _ptr(dop), _ptr(buf), buf.numel(), _ptr(comp))
+                                  _ptr(d_alpha), _ptr(dm2), _ptr(dcon), _ptr(dcol), _ptr(dop), _ptr(buf), buf.numel(), _ptr(comp), _ptr(dabs))
     L.check(L.load().v3a_gs_rasterize_backward(C.byref(a), _stream()), "v3a_gs_rasterize_backward")
-    return dict(d_means2d=dm2, d_conics=dcon, d_colors=dcol, d_opacity=dop)
+    out = dict(d_means2d=dm2, d_conics=dcon, d_colors=dcol, d_opacity=dop)
+    if absgrad:
+        out["d_means2d_abs"] = dabs
+    return out
 
 
 def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, viewmat: torch.Tensor, campos: torch.Tensor,
@@ -1190,7 +1196,7 @@ def gs_project_backward(means: torch.Tensor, covars: torch.Tensor, sh: torch.Ten
 class _GsRender(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means, covars, sh, opacities, viewmat, campos, K, width, height, sh_degree, sh_layout, background, clamp_rgb,
-                workspace, n_isect_out, rasterize_mode, camera_grad):
+                workspace, n_isect_out, rasterize_mode, camera_grad, info_out, absgrad):
         pr = gs_project(means, covars, sh, viewmat, campos, K, width, height, sh_degree=sh_degree, sh_layout=sh_layout,
                         rasterize_mode=rasterize_mode)
         r = gs_rasterize(pr, opacities, width, height, background=background, clamp_rgb=clamp_rgb, workspace=workspace, return_order=True)
@@ -1200,6 +1206,9 @@ class _GsRender(torch.autograd.Function):
                               r["tile_offsets"], r["flatten_ids"].contiguous(), *([pr["compensations"]] if "compensations" in pr else []))
         ctx.cfg = (width, height, sh_degree, sh_layout, background, clamp_rgb, workspace, rasterize_mode)
         ctx.camera_grad = camera_grad
+        ctx.info_out, ctx.absgrad = info_out, absgrad
+        if info_out is not None:
+            info_out["radii"] = pr["radii"]
         return r["color"], r["depth"], r["alpha"]
 
     @staticmethod
@@ -1215,22 +1224,28 @@ class _GsRender(torch.autograd.Function):
         if comp:
             pr["compensations"] = comp[0]
         eg = gs_rasterize_backward(pr, opacities, width, height, offs, ids, z(d_color, 3), z(d_depth), z(d_alpha), background=background,
-                                   clamp_rgb=clamp_rgb, workspace=workspace.bwd if workspace is not None else None)
+                                   clamp_rgb=clamp_rgb, workspace=workspace.bwd if workspace is not None else None,
+                                   absgrad=ctx.absgrad)
+        if ctx.info_out is not None:
+            ctx.info_out["d_means2d"] = eg["d_means2d"]
+            if ctx.absgrad:
+                ctx.info_out["d_means2d_abs"] = eg["d_means2d_abs"]
         if ctx.camera_grad:
             d_means, d_covars, d_sh, d_op, d_view, d_campos = gs_project_backward(
                 means, covars, sh, viewmat, campos, K, width, height, radii, eg, sh_degree=sh_degree, sh_layout=sh_layout,
                 rasterize_mode=rasterize_mode, opacities=opacities if comp else None, camera_grad=True)
-            return (d_means, d_covars, d_sh, d_op, d_view, d_campos) + (None,) * 11
+            return (d_means, d_covars, d_sh, d_op, d_view, d_campos) + (None,) * 13
         d_means, d_covars, d_sh, d_op = gs_project_backward(means, covars, sh, viewmat, campos, K, width, height, radii, eg,
                                                             sh_degree=sh_degree, sh_layout=sh_layout, rasterize_mode=rasterize_mode,
                                                             opacities=opacities if comp else None)
-        return (d_means, d_covars, d_sh, d_op) + (None,) * 13
+        return (d_means, d_covars, d_sh, d_op) + (None,) * 15
 
 
 def gs_render(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, opacities: torch.Tensor, viewmat: torch.Tensor,
               campos: torch.Tensor, K: torch.Tensor, width: int, height: int, *, sh_degree: int = 4, sh_layout: int = 1,
               background: Optional[torch.Tensor] = None, clamp_rgb: bool = True, workspace: Optional[GsWorkspace] = None,
-              n_isect_out: Optional[list] = None, rasterize_mode: str = "classic", camera_grad: bool = False):
+              n_isect_out: Optional[list] = None, rasterize_mode: str = "classic", camera_grad: bool = False,
+              info_out: Optional[dict] = None, absgrad: bool = False):
     """Differentiable gs_project + gs_rasterize for C cameras (viewmat [C,4,4], campos [C,3], K [C,3,3]) ->
     (color [C,H,W,3], depth [C,H,W], alpha [C,H,W]) with gradients to means, covars, sh and opacities through the HIP backward
     kernels (csrc/raster_bwd.hip).  The forward values are gs_rasterize's, bit for bit.  By default cameras are constants:
@@ -1238,8 +1253,13 @@ def gs_render(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, opaci
     campos that requires grad and hands it its gradient (v3a_gs_project_backward_cam; the other four gradients keep their bits);
     viewmat and campos are independent inputs here, so a pose reaches both through whatever computed them (ops.camera_adjust).
     K that requires grad is refused either way.  First-order only.
-    rasterize_mode="antialiased": gsplat's mode of that name, forward and backward (every entry's opacity times its compensation)."""
+    rasterize_mode="antialiased": gsplat's mode of that name, forward and backward (every entry's opacity times its compensation).
+    info_out: a dict that receives what the densification strategy reads, as gsplat's `info` does: "radii" [C,U] from the forward,
+    "d_means2d" [C,U,2] from the backward, and with absgrad=True "d_means2d_abs" [C,U,2] (see gs_rasterize_backward).  With None
+    (and absgrad=False) nothing changes."""
     _gs_mode(rasterize_mode)
+    if absgrad and info_out is None:
+        raise ValueError("gs_render: absgrad=True needs info_out (the dict that receives d_means2d_abs)")
     for t, n in ((viewmat, "viewmat"), (campos, "campos"), (K, "K")):
         if t.requires_grad and not (camera_grad and n != "K"):
             raise NotImplementedError(f"gs_render: no gradient for {n} (camera pose / intrinsics gradients are not implemented)"
@@ -1247,7 +1267,7 @@ def gs_render(means: torch.Tensor, covars: torch.Tensor, sh: torch.Tensor, opaci
     if viewmat.dim() != 3:
         raise ValueError("gs_render: viewmat [C,4,4], campos [C,3], K [C,3,3] required")
     return _GsRender.apply(means, covars, sh, opacities, viewmat, campos, K, width, height, sh_degree, sh_layout, background,
-                           clamp_rgb, workspace, n_isect_out, rasterize_mode, bool(camera_grad))
+                           clamp_rgb, workspace, n_isect_out, rasterize_mode, bool(camera_grad), info_out, bool(absgrad))
 
 
 class _CameraAdjust(torch.autograd.Function):
@@ -1827,7 +1847,9 @@ def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor
     L.check(L.load().v3a_adam_step(C.byref(a), _stream()), "v3a_adam_step")
 
 
-MCMC_STREAMS = dict(relocate=0, grow=1)   # the sampler's random streams (2 and 3 are the noise's draws)
+# the random streams of the strategies' Philox draws: the sampler's two (2 and 3 are the noise's draws), and the first of the two
+# consecutive streams of each split child of the densification (z0, z1 of stream s, z2 = z0 of stream s + 1)
+MCMC_STREAMS = dict(relocate=0, grow=1, split0=4, split1=6)
 
 
 def _mcmc_key(seed: int, step: int, what: str):
@@ -1911,3 +1933,111 @@ def mcmc_noise(means: torch.Tensor, log_scales: torch.Tensor, quats: torch.Tenso
     seed, step = _mcmc_key(seed, step, "mcmc_noise")
     L.check(L.load().v3a_mcmc_noise(_ptr(means), _ptr(log_scales), _ptr(quats), _ptr(logits), U, float(scaler), seed, step, _stream()),
             "v3a_mcmc_noise")
+
+
+# ------------------------------------------------------------------------------------------------ densification (csrc/densify.hip)
+def _i32_dev(t: torch.Tensor, name: str, shape) -> None:
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be a contiguous int32 device tensor of shape {tuple(shape)}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def densify_accumulate(grad2d: torch.Tensor, count: torch.Tensor, d_means2d: torch.Tensor, radii: torch.Tensor, width: int,
+                       height: int) -> None:
+    """The densification strategy's per-step statistics, in place on grad2d f32 [U] and count int32 [U]: for every camera c (index
+    order) with radii[c,g] > 0, grad2d[g] += sqrt((gx W/2 C)^2 + (gy H/2 C)^2) with (gx, gy) = d_means2d[c,g], count[g] += 1
+    (v3a_densify_accumulate: fp64 norm and sum, one rounding per call).  d_means2d f32 [C,U,2] and radii int32 [C,U] as
+    gs_render's info_out holds them."""
+    U = grad2d.shape[0] if grad2d.dim() == 1 else -1
+    if U < 0 or d_means2d.dim() != 3 or d_means2d.shape[0] < 1:
+        raise ValueError("densify_accumulate: grad2d [U] and d_means2d [C,U,2] required")
+    Cn = d_means2d.shape[0]
+    _f32_dev(grad2d, "grad2d", (U,))
+    _i32_dev(count, "count", (U,))
+    _f32_dev(d_means2d, "d_means2d", (Cn, U, 2))
+    _i32_dev(radii, "radii", (Cn, U))
+    if width < 1 or height < 1:
+        raise ValueError(f"densify_accumulate: width and height must be positive, got {width} x {height}")
+    if U == 0:
+        return
+    L.check(L.load().v3a_densify_accumulate(_ptr(d_means2d), _ptr(radii), U, Cn, int(width), int(height), _ptr(grad2d), _ptr(count), _stream()),
+            "v3a_densify_accumulate")
+
+
+def densify_classify(grad2d: torch.Tensor, count: torch.Tensor, log_scales: torch.Tensor, logits: torch.Tensor, *, grow_grad2d: float,
+                     grow_scale3d: float, prune_opa: float, prune_scale3d: float, grow: bool = True, prune_big: bool = False,
+                     revised_opacity: bool = False) -> dict:
+    """The fate of every Gaussian at a refine (v3a_densify_classify; fp64 decisions on exactly converted values; the two scale
+    thresholds come multiplied by the scene scale) -> dict(fates uint8 [U]: 0 keep, 1 clone, 2 split, + 4 when the rows it leaves
+    are pruned; counts int32 [3,U]: the rows it leaves in segment A (the original), B (the clone), C = D (each split child);
+    offsets int32 [3,U]: their exclusive prefix sums; totals int64 [3] on the device).  grow=False forces every fate to keep
+    (prune only); prune_big adds the scale criterion to the opacity criterion."""
+    U = grad2d.shape[0] if grad2d.dim() == 1 else -1
+    if U < 0:
+        raise ValueError("densify_classify: grad2d [U] required")
+    _f32_dev(grad2d, "grad2d", (U,))
+    _i32_dev(count, "count", (U,))
+    _f32_dev(log_scales, "log_scales", (U, 3))
+    _f32_dev(logits, "logits", (U,))
+    dev = grad2d.device
+    out = dict(fates=torch.empty(U, device=dev, dtype=torch.uint8), counts=torch.empty(3, U, device=dev, dtype=torch.int32),
+               offsets=torch.empty(3, U, device=dev, dtype=torch.int32), totals=torch.zeros(3, device=dev, dtype=torch.int64))
+    if U == 0:
+        return out
+    lib = L.load()
+    ws, ws_bytes = _workspace(lib.v3a_densify_classify_workspace_bytes(U), f"v3a_densify_classify_workspace_bytes (U = {U})", dev)
+    a = L.DensifyClassifyArgs(_ptr(grad2d), _ptr(count), _ptr(log_scales), _ptr(logits), U, float(grow_grad2d), float(grow_scale3d),
+                              float(prune_opa), float(prune_scale3d), int(bool(grow)), int(bool(prune_big)), int(bool(revised_opacity)),
+                              _ptr(out["fates"]), _ptr(out["counts"]), _ptr(out["offsets"]), _ptr(out["totals"]), _ptr(ws), ws_bytes)
+    L.check(lib.v3a_densify_classify(C.byref(a), _stream()), "v3a_densify_classify")
+    return out
+
+
+def densify_apply(cls: dict, params: dict, m: dict, v: dict, *, seed: int, step: int, revised_opacity: bool = False,
+                  totals: Optional[list] = None):
+    """The refined scene from densify_classify's `cls` and the old tensors (dicts of means [U,3], scales (logs) [U,3], quats [U,4],
+    opacities (logits) [U], sh [U,3,K], f32) -> (params, m, v): NEW dicts of tensors with U_out = A + B + 2 C rows in the order
+    A surviving non-split originals, B surviving clones, C first children, D second children (v3a_densify_apply; include/vist3a_hip.h
+    states a child's values).  The old tensors are read only.  `totals` = cls["totals"].tolist() if the caller has read it already;
+    otherwise it is read here: the refine's one read-back, which sizes the new tensors."""
+    U = cls["fates"].shape[0]
+    sh = params["sh"]
+    if sh.dim() != 3 or sh.shape[1] != 3 or sh.shape[2] < 1:
+        raise ValueError(f"densify_apply: sh must be [U,3,K], got {tuple(sh.shape)}")
+    K = sh.shape[2]
+    shapes = dict(means=(U, 3), scales=(U, 3), quats=(U, 4), opacities=(U,), sh=(U, 3, K))
+    for group, d in (("params", params), ("m", m), ("v", v)):
+        for name in _MCMC_TENSORS:
+            _f32_dev(d[name], f"{group}[{name!r}]", shapes[name])
+    if cls["fates"].dtype != torch.uint8 or not cls["fates"].is_cuda or not cls["fates"].is_contiguous():
+        raise ValueError("densify_apply: cls['fates'] must be a contiguous uint8 device vector")
+    _i32_dev(cls["offsets"], "cls['offsets']", (3, U))
+    if cls["totals"].dtype != torch.int64 or tuple(cls["totals"].shape) != (3,) or not cls["totals"].is_cuda:
+        raise ValueError("densify_apply: cls['totals'] must be int64 [3] on the device")
+    seed, step = _mcmc_key(seed, step, "densify_apply")
+    nA, nB, nC = (int(x) for x in (cls["totals"].tolist() if totals is None else totals))
+    U_out = nA + nB + 2 * nC
+    if min(nA, nB, nC) < 0 or nA + nB > 2 * U or nC > U or U_out >= 2 ** 31:
+        raise ValueError(f"densify_apply: segment totals {(nA, nB, nC)} do not belong to {U} Gaussians")
+    dev = sh.device
+    new = [{name: torch.empty((U_out,) + shapes[name][1:], device=dev, dtype=f32) for name in _MCMC_TENSORS} for _ in range(3)]
+    if U == 0 or U_out == 0:
+        return tuple(new)
+    a = L.DensifyApplyArgs(*(_ptr(d[name]) for d in (params, m, v, *new) for name in _MCMC_TENSORS), _ptr(cls["fates"]), _ptr(cls["offsets"]),
+                           _ptr(cls["totals"]), U, U_out, K, seed, step, int(bool(revised_opacity)))
+    L.check(L.load().v3a_densify_apply(C.byref(a), _stream()), "v3a_densify_apply")
+    return tuple(new)
+
+
+def densify_reset_opacity(logits: torch.Tensor, m: torch.Tensor, v: torch.Tensor, max_opacity: float) -> None:
+    """The strategy's opacity reset, in place: logits = min(logits, logit(max_opacity)), Adam's moments m and v of the logits = 0
+    (v3a_densify_reset_opacity)."""
+    U = logits.shape[0] if logits.dim() == 1 else -1
+    if U < 0:
+        raise ValueError("densify_reset_opacity: logits [U] required")
+    for name, t in (("logits", logits), ("m", m), ("v", v)):
+        _f32_dev(t, name, (U,))
+    if not 0.0 < float(max_opacity) < 1.0:
+        raise ValueError(f"densify_reset_opacity: max_opacity must lie in (0, 1), got {max_opacity!r}")
+    if U == 0:
+        return
+    L.check(L.load().v3a_densify_reset_opacity(_ptr(logits), _ptr(m), _ptr(v), U, float(max_opacity), _stream()), "v3a_densify_reset_opacity")

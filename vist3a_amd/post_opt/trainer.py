@@ -34,6 +34,16 @@ pose_opt_reg, torch's default eps 1e-8, rate decaying to 1 % over max_steps).  T
 here it is off by default so that no existing call changes - a stated deviation.  The deltas stay in
 `splats["pose_deltas"]`; adjusted_extrinsics turns them into cameras.
 
+cfg.strategy = "densify" is the reference's `default` configuration with its densification running (:1486-1491; the reference
+parks the schedule at :389-392; the value "default" stays refused, as it always was: in this package the reference's `default`
+as it runs is "none"): gsplat's DefaultStrategy, the classic 3DGS adaptive density control, restated in DESIGN.md section
+7f (again the contract).  After the Adam updates of a step the screen-space gradient of every visible Gaussian joins a running sum
+(ops.densify_accumulate, from gs_render's info_out); every cfg.densify_refine_every steps Gaussians whose average exceeds
+cfg.densify_grow_grad2d are cloned (small ones) or split in two (large ones), transparent and oversized ones are pruned
+(ops.densify_classify, ops.densify_apply: csrc/densify.hip), and every cfg.densify_reset_every steps the opacities are capped
+(ops.densify_reset_opacity).  One read-back per refine - the three segment sizes, which size the new tensors (gsplat syncs there
+too) - and a second one only when cfg.densify_cap_max turns a refine into prune-only.
+
 The harmonics stay ONE [U,3,K] tensor: the reference's sh0 / shN optimisers (rates lr_sh and lr_sh / 20) are one ops.adam_step with
 a period of K, which is the same arithmetic because Adam is elementwise."""
 from __future__ import annotations
@@ -75,13 +85,26 @@ class PostOptConfig:
     random_bkgd: bool = False        # :326-327: a random background per step, to discourage transparency
     opacity_reg: float = 0.0         # :329-330: weight of mean sigmoid(logit), added when > 0
     scale_reg: float = 0.0           # :331-332: weight of mean exp(log-scale), added when > 0
-    strategy: str = "none"           # "none" (the reference's `default`: densification off, :389-392) or "mcmc" (:1485-1501)
+    strategy: str = "none"           # "none" (the reference's `default` as it runs: densification parked, :389-392), "mcmc" (:1485-1501) or
+                                     # "densify" (the reference's `default` with gsplat's DefaultStrategy running, :1486-1491)
     mcmc_cap_max: int = 1_000_000    # gsplat MCMCStrategy's defaults from here on: the scene stops growing at this many Gaussians
     mcmc_noise_lr: float = 5e5       # the noise is scaled by mcmc_noise_lr * (the means' current learning rate)
     mcmc_refine_start_iter: int = 500
     mcmc_refine_stop_iter: int = 25_000
     mcmc_refine_every: int = 100
     mcmc_min_opacity: float = 0.005  # at or below it a Gaussian is dead: relocated at the next refine
+    densify_prune_opa: float = 0.005       # gsplat DefaultStrategy's defaults from here on: rows below this opacity are pruned
+    densify_grow_grad2d: float = 2e-4      # average screen-space gradient above which a Gaussian is cloned or split
+    densify_grow_scale3d: float = 0.01     # (x scene_scale) largest scale up to which it is cloned, above which it is split
+    densify_prune_scale3d: float = 0.1     # (x scene_scale) largest scale above which a row is pruned, once i > densify_reset_every
+    densify_refine_start_iter: int = 500
+    densify_refine_stop_iter: int = 15_000
+    densify_reset_every: int = 3000
+    densify_refine_every: int = 100
+    densify_pause_refine_after_reset: int = 0
+    densify_absgrad: bool = False          # accumulate gsplat's absgrad (sum of absolute per-pixel gradients) instead of the gradient
+    densify_revised_opacity: bool = False  # split children get opacity 1 - sqrt(1 - o) (arXiv:2404.06109) instead of o
+    densify_cap_max: int = 0               # ours: > 0, a refine that would pass this many Gaussians prunes only
     test_every: int = 0              # k > 0: the views with index % k == 0 are held out of the loop (the reference's dataset split, test_every)
     pose_opt: bool = False           # :335-336; True in the reference - off here so that existing calls keep their bits (a stated deviation)
     pose_opt_lr: float = 1e-5        # :337
@@ -102,9 +125,30 @@ class PostOptConfig:
         return tuple(n for n in PARAM_NAMES if n in names)
 
     def check_strategy(self) -> None:
-        if self.strategy not in ("none", "mcmc"):
-            raise ValueError(f"PostOptConfig.strategy must be 'none' or 'mcmc', got {self.strategy!r}")
+        if self.strategy not in ("none", "mcmc", "densify"):
+            raise ValueError(f"PostOptConfig.strategy must be 'none', 'mcmc' or 'densify' (the reference's `default` configuration is 'none' as it runs there, 'densify' with its DefaultStrategy running), got {self.strategy!r}")
         if self.strategy == "none":
+            return
+        if isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f"PostOptConfig.seed keys the strategy's random numbers: an integer in [0, 2^64), got {self.seed!r}")
+        if self.strategy == "densify":
+            ints = {n: getattr(self, n) for n in ("densify_refine_start_iter", "densify_refine_stop_iter", "densify_reset_every",
+                                                  "densify_refine_every", "densify_pause_refine_after_reset", "densify_cap_max")}
+            for name, n in ints.items():
+                if not isinstance(n, int) or isinstance(n, bool) or n < 0:
+                    raise ValueError(f"PostOptConfig.{name} must be a non-negative integer, got {n!r}")
+            if self.densify_refine_every < 1 or self.densify_reset_every < 1:
+                raise ValueError(f"PostOptConfig.densify_refine_every and densify_reset_every must be positive, got "
+                                 f"{self.densify_refine_every!r} and {self.densify_reset_every!r}")
+            if not 0.0 < self.densify_prune_opa < 0.5:
+                raise ValueError(f"PostOptConfig.densify_prune_opa must lie in (0, 0.5) (the reset caps opacities at twice it), got "
+                                 f"{self.densify_prune_opa!r}")
+            for name in ("densify_grow_grad2d", "densify_grow_scale3d", "densify_prune_scale3d", "scene_scale"):
+                if not getattr(self, name) > 0:
+                    raise ValueError(f"PostOptConfig.{name} must be positive, got {getattr(self, name)!r}")
+            for name in ("densify_absgrad", "densify_revised_opacity"):
+                if not isinstance(getattr(self, name), bool):
+                    raise ValueError(f"PostOptConfig.{name} must be a bool, got {getattr(self, name)!r}")
             return
         ints = dict(mcmc_cap_max=self.mcmc_cap_max, mcmc_refine_start_iter=self.mcmc_refine_start_iter,
                     mcmc_refine_stop_iter=self.mcmc_refine_stop_iter, mcmc_refine_every=self.mcmc_refine_every)
@@ -117,8 +161,6 @@ class PostOptConfig:
         if not self.mcmc_noise_lr >= 0 or not 0.0 < self.mcmc_min_opacity < 1.0:
             raise ValueError(f"PostOptConfig.mcmc_noise_lr must be non-negative and mcmc_min_opacity in (0, 1), got "
                              f"{self.mcmc_noise_lr!r} and {self.mcmc_min_opacity!r}")
-        if isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 2 ** 64:
-            raise ValueError(f"PostOptConfig.seed keys the strategy's random numbers: an integer in [0, 2^64), got {self.seed!r}")
 
     def check_pose(self) -> None:
         if not isinstance(self.pose_opt, bool):
@@ -223,6 +265,70 @@ def mcmc_refine(splats: dict, cfg: PostOptConfig, t: int) -> None:
             ops.mcmc_relocate(src, counts, p, m, v, dst_offset=U, min_opacity=cfg.mcmc_min_opacity)
         row = torch.stack([relocated, torch.full((), n, device=dev, dtype=torch.int64)])[None]
         splats["mcmc_counts"] = torch.cat([splats["mcmc_counts"], row]) if "mcmc_counts" in splats else row
+
+
+def densify_active_at(cfg: PostOptConfig, i: int) -> bool:
+    """Whether the densification strategy does anything after the Adam updates of 0-based step `i`: gsplat returns at once when
+    step >= refine_stop_iter (no statistics, no refine, no reset)."""
+    return i < cfg.densify_refine_stop_iter
+
+
+def densify_refines_at(cfg: PostOptConfig, i: int) -> bool:
+    """Whether it refines after step `i`: gsplat's step > refine_start_iter and step % refine_every == 0 and
+    step % reset_every >= pause_refine_after_reset."""
+    return (densify_active_at(cfg, i) and i > cfg.densify_refine_start_iter and i % cfg.densify_refine_every == 0
+            and i % cfg.densify_reset_every >= cfg.densify_pause_refine_after_reset)
+
+
+def densify_resets_at(cfg: PostOptConfig, i: int) -> bool:
+    """Whether it resets the opacities after step `i`: gsplat's step % reset_every == 0, and i > 0 (ours: gsplat also resets after
+    the very first step, which would cap the predicted opacities before anything was learnt)."""
+    return densify_active_at(cfg, i) and i > 0 and i % cfg.densify_reset_every == 0
+
+
+def densify_state(splats: dict) -> dict:
+    """splats["densify"] = {"grad2d": f32 [U], "count": int32 [U]}, the running statistics, created as zeros when missing"""
+    U, dev = splats["params"]["means"].shape[0], splats["params"]["means"].device
+    st = splats.get("densify")
+    if st is None:
+        st = splats["densify"] = dict(grad2d=torch.zeros(U, device=dev, dtype=torch.float32), count=torch.zeros(U, device=dev, dtype=torch.int32))
+    if tuple(st["grad2d"].shape) != (U,) or tuple(st["count"].shape) != (U,):
+        raise ValueError(f"splats['densify'] holds statistics of {tuple(st['grad2d'].shape)} Gaussians, the scene has {U}")
+    return st
+
+
+def densify_refine(splats: dict, cfg: PostOptConfig, i: int) -> None:
+    """One refine after the Adam updates of 0-based step `i`, on the updated parameters: classify (clone / split / keep, then the
+    prune verdict of the rows each parent leaves), read the three segment sizes back, and REPLACE the fifteen tensors of params / m / v
+    by new ones in gsplat's row order (surviving originals, clones, first children, second children; new rows start with zero
+    moments).  The split children's offsets are drawn from Philox streams 4-7 at counter (parent, 0, stream, i + 1) under cfg.seed.
+    With cfg.densify_cap_max > 0, a refine that would exceed it is classified again with growth off (one more read-back) and prunes
+    only.  The statistics restart as zeros at the new length.  Appends (cloned, split, pruned, U_after) to splats["densify_counts"],
+    int64 [refines,4] on the device: surviving clones, split parents whose children survive, parents whose rows were pruned.
+    A refine that leaves no Gaussian raises RuntimeError."""
+    p, m, v = splats["params"], splats["m"], splats["v"]
+    U, dev = p["means"].shape[0], p["means"].device
+    st = densify_state(splats)
+    with torch.no_grad():
+        kw = dict(grow_grad2d=cfg.densify_grow_grad2d, grow_scale3d=cfg.densify_grow_scale3d * cfg.scene_scale,
+                  prune_opa=cfg.densify_prune_opa, prune_scale3d=cfg.densify_prune_scale3d * cfg.scene_scale,
+                  prune_big=i > cfg.densify_reset_every, revised_opacity=cfg.densify_revised_opacity)
+        cls = ops.densify_classify(st["grad2d"], st["count"], p["scales"].detach(), p["opacities"].detach(), grow=True, **kw)
+        nA, nB, nC = cls["totals"].tolist()                    # the refine's read-back
+        if cfg.densify_cap_max > 0 and nA + nB + 2 * nC > cfg.densify_cap_max:
+            cls = ops.densify_classify(st["grad2d"], st["count"], p["scales"].detach(), p["opacities"].detach(), grow=False, **kw)
+            nA, nB, nC = cls["totals"].tolist()
+        U_out = nA + nB + 2 * nC
+        if U_out == 0:
+            raise RuntimeError(f"densification pruned all {U} Gaussians at step {i} (densify_prune_opa = {cfg.densify_prune_opa}, "
+                               f"densify_prune_scale3d = {cfg.densify_prune_scale3d})")
+        new = ops.densify_apply(cls, {k: t.detach() for k, t in p.items()}, m, v, seed=cfg.seed, step=i + 1,
+                                revised_opacity=cfg.densify_revised_opacity, totals=(nA, nB, nC))
+        for d, nd in zip((p, m, v), new):
+            d.update(nd)
+        splats["densify"] = dict(grad2d=torch.zeros(U_out, device=dev, dtype=torch.float32), count=torch.zeros(U_out, device=dev, dtype=torch.int32))
+        row = torch.tensor([[nB, nC, U + nB + nC - U_out, U_out]], device=dev, dtype=torch.int64)
+        splats["densify_counts"] = torch.cat([splats["densify_counts"], row]) if "densify_counts" in splats else row
 
 
 def train_views(n_views: int, test_every: int) -> list:
@@ -389,7 +495,16 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     Update: ops.adam_step(deltas, grad + cfg.pose_opt_reg * deltas, lr = pose_learning_rate(cfg, steps done), betas (0.9, 0.999),
     eps 1e-8) - torch.optim.Adam(weight_decay) restated; every row moves each step.  cfg.params may then be empty (a pose-only fit).
     `extrinsics` that require grad are still refused: the deltas are the loop's own state.  adjusted_extrinsics(extrinsics, splats,
-    cfg) returns the refined cameras; held-out views keep their given poses.  The log has no column of its own for it."""
+    cfg) returns the refined cameras; held-out views keep their given poses.  The log has no column of its own for it.
+
+    With cfg.strategy = "densify", after the Adam updates of 0-based step i (while densify_active_at(cfg, i)): ops.densify_accumulate
+    adds the step's screen-space gradients (gs_render's info_out; the absolute ones with cfg.densify_absgrad) to splats["densify"] =
+    {"grad2d": f32 [U], "count": int32 [U]}; if densify_refines_at(cfg, i), densify_refine (the tensors in `splats` are replaced, the
+    returned Gaussians follow the new count; splats["densify_counts"], int64 [refines,4], holds (cloned, split, pruned, U_after));
+    if densify_resets_at(cfg, i), ops.densify_reset_opacity caps the opacities at 2 cfg.densify_prune_opa and zeroes their moments.
+    A `splats` carried through several calls continues where it was, as MCMC's state does.  Each refine reads the three segment
+    sizes back to the host (they size the new tensors; gsplat synchronises there too) - beside the rasteriser's intersection count
+    the loop's only read-back."""
     cfg = cfg or PostOptConfig()
     cfg.check_bilagrid()
     cfg.check_strategy()
@@ -455,6 +570,10 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     decay = 0.01 ** (1.0 / cfg.max_steps)
     ws = ops.GsWorkspace()
     mcmc = cfg.strategy == "mcmc"
+    densify = cfg.strategy == "densify"
+    if densify:
+        densify_state(splats)
+    extra = dict(info_out={}, absgrad=cfg.densify_absgrad) if densify else {}    # what the densification reads of every render
     leaves = [p[n].requires_grad_(True) for n in trained]
     if bil:
         leaves.append(splats["bil_grids"].requires_grad_(True))
@@ -468,11 +587,11 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
                 view_j, campos_j = ops.camera_adjust(w2c_base[j:j + 1], c2w_base[j:j + 1], splats["pose_deltas"][g_:g_ + 1])
                 color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view_j, campos_j, Kpix[j:j + 1], W, H,
                                             sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
-                                            clamp_rgb=True, workspace=ws, rasterize_mode=mode, camera_grad=True)
+                                            clamp_rgb=True, workspace=ws, rasterize_mode=mode, camera_grad=True, **extra)
             else:
                 color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
                                             sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
-                                            clamp_rgb=True, workspace=ws, rasterize_mode=mode)
+                                            clamp_rgb=True, workspace=ws, rasterize_mode=mode, **extra)
             if bil:
                 color = ops.bilagrid_slice(color, splats["bil_grids"][grid_of[j]:grid_of[j] + 1])
             loss, l1, ssim = ops.photometric_loss(color, images[j:j + 1], cfg.ssim_lambda)
@@ -517,6 +636,15 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
                         leaves = [p[n].requires_grad_(True) for n in trained] + leaves[len(trained):]    # a grown scene has new tensors
                     ops.mcmc_noise(p["means"], p["scales"], p["quats"], p["opacities"], scaler=cfg.mcmc_noise_lr * (cfg.lr_means * decay ** t),
                                    seed=cfg.seed, step=t)
+                if densify and densify_active_at(cfg, t - 1):
+                    info, st = extra["info_out"], densify_state(splats)
+                    ops.densify_accumulate(st["grad2d"], st["count"], info["d_means2d_abs" if cfg.densify_absgrad else "d_means2d"],
+                                           info["radii"], W, H)
+                    if densify_refines_at(cfg, t - 1):
+                        densify_refine(splats, cfg, t - 1)
+                        leaves = [p[n].requires_grad_(True) for n in trained] + leaves[len(trained):]    # new tensors
+                    if densify_resets_at(cfg, t - 1):
+                        ops.densify_reset_opacity(p["opacities"].detach(), m["opacities"], v["opacities"], 2.0 * cfg.densify_prune_opa)
             splats["step"] = t
     finally:
         for n in trained:

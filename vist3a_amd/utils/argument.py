@@ -68,6 +68,20 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
                    help="the MCMC strategy stops adding Gaussians at N (a scene already above N only relocates)")
     g.add_argument("--post_opt_mcmc_refine", type=str, default="500,25000,100", metavar="START,STOP,EVERY",
                    help="the MCMC strategy refines after the steps i with START < i < STOP and i %% EVERY == 0 (counted from 0)")
+    g.add_argument("--post_opt_densify", action="store_true",
+                   help="post-optimise with adaptive density control (the reference's `default` configuration with gsplat's "
+                        "DefaultStrategy running): where the screen-space gradient is high small Gaussians are cloned and large ones "
+                        "split, transparent and oversized ones are pruned, the opacities are reset periodically.  Not with --post_opt_mcmc")
+    g.add_argument("--post_opt_densify_refine", type=str, default="500,15000,100,3000", metavar="START,STOP,EVERY,RESET",
+                   help="densification refines after the steps i with START < i < STOP and i %% EVERY == 0 (counted from 0) and resets "
+                        "the opacities every RESET steps")
+    g.add_argument("--post_opt_densify_grad", type=float, default=2e-4, metavar="X",
+                   help="average screen-space gradient above which a Gaussian is cloned or split (gsplat's grow_grad2d)")
+    g.add_argument("--post_opt_densify_absgrad", action="store_true",
+                   help="densify on the sum of absolute per-pixel gradients (gsplat's absgrad; wants a larger --post_opt_densify_grad, "
+                        "gsplat suggests 8e-4)")
+    g.add_argument("--post_opt_densify_cap_max", type=int, default=0, metavar="N",
+                   help="a refine that would pass N Gaussians only prunes; 0 = no cap")
     g.add_argument("--post_opt_pose_opt", action="store_true",
                    help="refine the predicted camera poses together with the scene (the reference's pose_opt, on by default there): 9 "
                         "deltas per training view train through the rasteriser's camera gradients; the adjusted cameras are written to "
