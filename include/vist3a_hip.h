@@ -38,7 +38,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 32) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 34) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -956,6 +956,59 @@ int v3a_densify_apply(const v3a_densify_apply_args* a, void* stream);
 /* Opacity reset: logit = min(logit, logit(max_opacity)) (fp64 compare, one rounding), m = v = 0, elementwise on [U];
  * max_opacity in (0, 1) (else V3A_ERR_SHAPE). */
 int v3a_densify_reset_opacity(float* logits, float* m_logits, float* v_logits, long U, double max_opacity, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Scene export packed on the device (csrc/splat_export.hip; the reference's post_opt/exporter.py export_splats: `ply`, `splat`,
+ * `ply_compressed`).  DESIGN.md section 7g states the formats.  All five entry points take one struct.
+ *
+ * Scene: means f32 [U,3], log-scales f32 [U,3], quaternions f32 [U,4] (quats_xyzw != 0: stored x y z w; else w x y z, the files'
+ * order), opacity logits f32 [U], harmonics f32 [U,3,K+1] with coefficient 0 the DC term (f_rest_j, j = c K + k, is sh[u][c][1+k]);
+ * K >= 0.  ld_*: row strides in ELEMENTS (>= 3, 3, 4, 1, 3 (K+1); a row's own elements are contiguous).  0 <= U < 2^31, K <= 1024
+ * (V3A_ERR_SHAPE otherwise).  fp32 throughout, no contraction: a*b + c is two roundings and every division an IEEE division.
+ *
+ * v3a_splat_export_filter: rows[0 .. *count) = the rows, in ascending order, none of whose values is NaN or Inf and - with
+ *   filter_opacity != 0 - whose 1 / (1 + exp(-logit)) > opacity_threshold.  rows int32 [U]; count int64 [1] on the DEVICE (the host
+ *   may read it once to size the file).  A flag per row, an integer scan over blocks of 256, one scatter; no atomics.
+ *   workspace: v3a_splat_export_filter_workspace_bytes(U, K), 8-byte aligned (too small or misaligned: V3A_ERR_WORKSPACE).
+ * v3a_splat_export_sort: order[0 .. n) = rows[0 .. n) by the 30-bit Morton key of their means: per axis
+ *   (int32) floor((c - min) / len * 1024) & 0x3ff with min / max over these n rows and a zero length replaced by 1 (the maximum's
+ *   1024 becomes 0), bits interleaved with z highest; rocPRIM radix_sort_pairs, stable: equal keys keep ascending row index.
+ *   n = the filter's count, as the host read it; order int32 [n].  workspace: v3a_splat_export_sort_workspace_bytes(U, K).
+ * v3a_splat_export_pack_compressed (from order): chunk c = sorted splats [256 c, min(256 c + 256, n)).
+ *   out_chunks f32 [ceil(n / 256), 18]: min xyz, max xyz of the means; min, max of the log-scales, each clamped to [-20, 20] AFTER
+ *     the min / max; min rgb, max rgb of sh0 * 0.28209479 + 0.5.
+ *   out_vertices u32 [n,4] (16-byte aligned): position 11-10-11 and scale 11-10-11 of unorm((x - min) / (max - min)); rotation:
+ *     q / |q|, largest |component| (lowest index on ties) made positive, its index in bits 31:30, the other three as
+ *     unorm10(v * sqrt(2)/2 + 0.5); colour 8-8-8 and unorm8(1 / (1 + exp(-logit))).  unorm_b(v) = clamp(floor(v (2^b - 1) + 0.5), 0,
+ *     2^b - 1), and a NaN - the 0 / 0 of a channel whose max == min - gives 0 BY DEFINITION.
+ *   out_sh u8 [n, 3K] (4-byte aligned): clamp(trunc((x / 8 + 0.5) * 256), 0, 255) of f_rest_0 .. f_rest_{3K-1}.
+ * v3a_splat_export_pack_splat (from order): out_splat [n, 32 bytes] (16-byte aligned): means f32 x 3, exp(log-scale) f32 x 3,
+ *   trunc(clamp((rgb, sigmoid) * 255, 0, 255)) u8 x 4, trunc(clamp(q / |q| * 128 + 128, 0, 255)) u8 x 4 (w x y z).
+ * v3a_splat_export_pack_ply (from rows, unsorted): out_ply f32 [n, 14 + 3K]: x y z, f_dc_0..2, f_rest_*, logit, log-scales, w x y z.
+ * Every output element is written exactly once with plain stores; nothing else is written.  n == 0 is a no-op.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *means, *log_scales, *quats, *logits, *sh;
+  long ld_means, ld_log_scales, ld_quats, ld_logits, ld_sh;
+  long U;
+  int K, quats_xyzw;
+  int filter_opacity; float opacity_threshold;   /* filter only */
+  int* rows;        /* filter: out [U]; sort, pack_ply: in [n] */
+  long* count;      /* filter: out [1], device */
+  long n;           /* sort, pack_*: the survivors, <= U */
+  int* order;       /* sort: out [n]; pack_compressed, pack_splat: in */
+  float* out_chunks; unsigned int* out_vertices; unsigned char* out_sh;   /* pack_compressed */
+  unsigned char* out_splat;                                                /* pack_splat */
+  float* out_ply;                                                          /* pack_ply */
+  void* workspace; long workspace_bytes;                                   /* filter, sort */
+} v3a_splat_export_args;
+long v3a_splat_export_filter_workspace_bytes(long U, int K);   /* V3A_ERR_SHAPE for U < 0, U >= 2^31, K < 0 or K > 1024 */
+int v3a_splat_export_filter(const v3a_splat_export_args* a, void* stream);
+long v3a_splat_export_sort_workspace_bytes(long U, int K);
+int v3a_splat_export_sort(const v3a_splat_export_args* a, void* stream);
+int v3a_splat_export_pack_compressed(const v3a_splat_export_args* a, void* stream);
+int v3a_splat_export_pack_splat(const v3a_splat_export_args* a, void* stream);
+int v3a_splat_export_pack_ply(const v3a_splat_export_args* a, void* stream);
 
 #ifdef __cplusplus
 }

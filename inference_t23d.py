@@ -27,6 +27,7 @@ from vist3a_amd.t23d import Text23DGS, synthetic_text_embeddings  # noqa: E402
 from vist3a_amd.utils.argument import inference_vist3a_argument  # noqa: E402
 from vist3a_amd.utils.dist_util import setup_dist, shard_prompts  # noqa: E402
 from vist3a_amd.utils.ply_export import export_ply  # noqa: E402
+from vist3a_amd.utils.splat_export import FILE_NAMES as EXPORT_FILE_NAMES, export_gaussians, parse_formats as parse_export_formats  # noqa: E402
 from vist3a_amd.wan.dit import WAN_1_3B, WAN_14B, WanDiT  # noqa: E402
 from vist3a_amd.wan.weights import load_dit_config, load_dit_state_dict, load_peft_lora, random_dit_state_dict  # noqa: E402
 
@@ -195,6 +196,9 @@ def main(args):
         raise ValueError("--post_opt_opacity_reg and --post_opt_scale_reg are weights >= 0")
     mcmc = mcmc_options(args)
     densify = densify_options(args)
+    export_formats = parse_export_formats(args.export_format)
+    if args.export_sh_rest and not export_formats:
+        raise ValueError("--export_sh_rest needs --export_format (it is an option of the extra scene files)")
     if (args.post_opt_pose_opt or args.post_opt_pose_lr is not None) and args.post_opt_steps <= 0:
         raise ValueError("--post_opt_pose_opt / --post_opt_pose_lr need --post_opt_steps > 0 (the poses are refined by the post-optimisation)")
     if args.post_opt_pose_lr is not None and not args.post_opt_pose_lr > 0:
@@ -246,6 +250,8 @@ def main(args):
             finally:
                 decoder.rasterize_mode = mode
         export_ply(g.means[0], g.scales[0], g.rotations[0], g.harmonics[0], g.opacities[0], save / "gaussians.ply", save_sh_dc_only=True)
+        for fmt in export_formats:   # extra files only: gaussians.ply above is written as without the flag
+            export_gaussians(g, save / EXPORT_FILE_NAMES[fmt], fmt, sh_rest=args.export_sh_rest)
         print(f"[rank {rank}] {save}: {g.means.shape[1]} gaussians", flush=True)
     if world > 1:
         dist.barrier()

@@ -344,6 +344,19 @@ class DensifyApplyArgs(C.Structure):
     )
 
 
+class SplatExportArgs(C.Structure):
+    _fields_ = (
+        [(f, C.c_void_p) for f in _DENSIFY_FIELDS]
+        + [("ld_" + f, C.c_long) for f in _DENSIFY_FIELDS]
+        + [("U", C.c_long), ("K", C.c_int), ("quats_xyzw", C.c_int),
+           ("filter_opacity", C.c_int), ("opacity_threshold", C.c_float),
+           ("rows", C.c_void_p), ("count", C.c_void_p), ("n", C.c_long), ("order", C.c_void_p),
+           ("out_chunks", C.c_void_p), ("out_vertices", C.c_void_p), ("out_sh", C.c_void_p), ("out_splat", C.c_void_p),
+           ("out_ply", C.c_void_p),
+           ("workspace", C.c_void_p), ("workspace_bytes", C.c_long)]
+    )
+
+
 # name -> (restype, argtypes); every symbol include/vist3a_hip.h declares must be listed here
 SYMBOLS = {
     "v3a_abi_version": (C.c_int, []),
@@ -450,10 +463,17 @@ SYMBOLS = {
     "v3a_densify_classify": (C.c_int, [C.POINTER(DensifyClassifyArgs), C.c_void_p]),
     "v3a_densify_apply": (C.c_int, [C.POINTER(DensifyApplyArgs), C.c_void_p]),
     "v3a_densify_reset_opacity": (C.c_int, [C.c_void_p] * 3 + [C.c_long, C.c_double, C.c_void_p]),
+    "v3a_splat_export_filter_workspace_bytes": (C.c_long, [C.c_long, C.c_int]),
+    "v3a_splat_export_filter": (C.c_int, [C.POINTER(SplatExportArgs), C.c_void_p]),
+    "v3a_splat_export_sort_workspace_bytes": (C.c_long, [C.c_long, C.c_int]),
+    "v3a_splat_export_sort": (C.c_int, [C.POINTER(SplatExportArgs), C.c_void_p]),
+    "v3a_splat_export_pack_compressed": (C.c_int, [C.POINTER(SplatExportArgs), C.c_void_p]),
+    "v3a_splat_export_pack_splat": (C.c_int, [C.POINTER(SplatExportArgs), C.c_void_p]),
+    "v3a_splat_export_pack_ply": (C.c_int, [C.POINTER(SplatExportArgs), C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 33   # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 34  # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

@@ -2041,3 +2041,106 @@ def densify_reset_opacity(logits: torch.Tensor, m: torch.Tensor, v: torch.Tensor
     if U == 0:
         return
     L.check(L.load().v3a_densify_reset_opacity(_ptr(logits), _ptr(m), _ptr(v), U, float(max_opacity), _stream()), "v3a_densify_reset_opacity")
+
+
+# ------------------------------------------------------------------------------------------------ scene export (csrc/splat_export.hip)
+def _export_scene(scene: dict, quats_xyzw: bool, what: str) -> L.SplatExportArgs:
+    """The scene part of v3a_splat_export_args from dict(means [U,3], scales (logs) [U,3], quats [U,4], opacities (logits) [U],
+    sh [U,3,K+1]): float32 device tensors whose rows may be strided (a row's own elements contiguous)."""
+    means, sh = scene["means"], scene["sh"]
+    if means.dim() != 2 or means.shape[1] != 3 or sh.dim() != 3 or sh.shape[1] != 3 or sh.shape[2] < 1:
+        raise ValueError(f"{what}: means [U,3] and sh [U,3,K+1] required, got {tuple(means.shape)} and {tuple(sh.shape)}")
+    U, K = means.shape[0], sh.shape[2] - 1
+    inner = dict(means=(3,), scales=(3,), quats=(4,), opacities=(), sh=(3, K + 1))
+    a = L.SplatExportArgs()
+    for field, name in zip(L._DENSIFY_FIELDS, _MCMC_TENSORS):
+        t = scene[name]
+        if not t.is_cuda or t.dtype != f32:
+            raise ValueError(f"{what}: {name} must be a float32 device tensor (the HIP path has no CPU fallback), got {t.dtype} on {t.device}")
+        if tuple(t.shape) != (U,) + inner[name]:
+            raise ValueError(f"{what}: {name} must have shape {(U,) + inner[name]}, got {tuple(t.shape)}")
+        width = 1
+        for n in inner[name]:
+            width *= n
+        if U > 0 and width > 1 and not t[0].is_contiguous():
+            raise ValueError(f"{what}: the elements of a row of {name} must be contiguous, got strides {t.stride()}")
+        ld = t.stride(0) if U > 1 else width
+        if ld < width:
+            raise ValueError(f"{what}: rows of {name} overlap (row stride {ld} < {width})")
+        setattr(a, field, t.data_ptr())
+        setattr(a, "ld_" + field, ld)
+    a.U, a.K, a.quats_xyzw = U, K, int(bool(quats_xyzw))
+    return a
+
+
+def _export_list(t: torch.Tensor, name: str, n: int, U: int) -> None:
+    if not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() or t.shape[0] < n or not 0 <= n <= U:
+        raise ValueError(f"{name} must be a contiguous int32 device vector of at least n = {n} <= {U} entries, got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+
+def splat_export_filter(scene: dict, *, quats_xyzw: bool, opacity_threshold: Optional[float] = None):
+    """The rows that go into an export (v3a_splat_export_filter): every value finite and, with `opacity_threshold`,
+    1 / (1 + exp(-logit)) above it.  -> (rows int32 [U], of which the first `count` are set, in ascending order; count int64 [1] on
+    the device - reading it is the caller's one synchronisation)."""
+    a = _export_scene(scene, quats_xyzw, "splat_export_filter")
+    dev = scene["means"].device
+    rows, count = torch.empty(a.U, device=dev, dtype=torch.int32), torch.zeros(1, device=dev, dtype=torch.int64)
+    if a.U == 0:
+        return rows, count
+    lib = L.load()
+    ws, ws_bytes = _workspace(lib.v3a_splat_export_filter_workspace_bytes(a.U, a.K), f"v3a_splat_export_filter_workspace_bytes (U = {a.U})", dev)
+    a.filter_opacity, a.opacity_threshold = int(opacity_threshold is not None), float(opacity_threshold or 0.0)
+    a.rows, a.count, a.workspace, a.workspace_bytes = rows.data_ptr(), count.data_ptr(), ws.data_ptr(), ws_bytes
+    L.check(lib.v3a_splat_export_filter(C.byref(a), _stream()), "v3a_splat_export_filter")
+    return rows, count
+
+
+def splat_export_sort(scene: dict, rows: torch.Tensor, n: int, *, quats_xyzw: bool) -> torch.Tensor:
+    """rows[:n] in the Morton order of their means, equal keys in ascending row order (v3a_splat_export_sort) -> int32 [n]."""
+    a = _export_scene(scene, quats_xyzw, "splat_export_sort")
+    _export_list(rows, "rows", n, a.U)
+    order = torch.empty(n, device=rows.device, dtype=torch.int32)
+    if n == 0:
+        return order
+    lib = L.load()
+    ws, ws_bytes = _workspace(lib.v3a_splat_export_sort_workspace_bytes(a.U, a.K), f"v3a_splat_export_sort_workspace_bytes (U = {a.U})", rows.device)
+    a.rows, a.n, a.order, a.workspace, a.workspace_bytes = rows.data_ptr(), n, order.data_ptr(), ws.data_ptr(), ws_bytes
+    L.check(lib.v3a_splat_export_sort(C.byref(a), _stream()), "v3a_splat_export_sort")
+    return order
+
+
+def splat_export_pack_compressed(scene: dict, order: torch.Tensor, n: int, *, quats_xyzw: bool):
+    """The compressed PLY's three elements of the splats order[:n] (v3a_splat_export_pack_compressed) -> (chunks f32 [ceil(n/256),18],
+    vertices int32 [n,4] (the packed words' bits), sh uint8 [n,3K])."""
+    a = _export_scene(scene, quats_xyzw, "splat_export_pack_compressed")
+    _export_list(order, "order", n, a.U)
+    dev = order.device
+    chunks = torch.empty((n + 255) // 256, 18, device=dev, dtype=f32)
+    vertices = torch.empty(n, 4, device=dev, dtype=torch.int32)
+    sh = torch.empty(n, 3 * a.K, device=dev, dtype=torch.uint8)
+    if n:
+        a.order, a.n, a.out_chunks, a.out_vertices, a.out_sh = order.data_ptr(), n, chunks.data_ptr(), vertices.data_ptr(), sh.data_ptr()
+        L.check(L.load().v3a_splat_export_pack_compressed(C.byref(a), _stream()), "v3a_splat_export_pack_compressed")
+    return chunks, vertices, sh
+
+
+def splat_export_pack_splat(scene: dict, order: torch.Tensor, n: int, *, quats_xyzw: bool) -> torch.Tensor:
+    """The .splat records of the splats order[:n] (v3a_splat_export_pack_splat) -> uint8 [n,32]."""
+    a = _export_scene(scene, quats_xyzw, "splat_export_pack_splat")
+    _export_list(order, "order", n, a.U)
+    out = torch.empty(n, 32, device=order.device, dtype=torch.uint8)
+    if n:
+        a.order, a.n, a.out_splat = order.data_ptr(), n, out.data_ptr()
+        L.check(L.load().v3a_splat_export_pack_splat(C.byref(a), _stream()), "v3a_splat_export_pack_splat")
+    return out
+
+
+def splat_export_pack_ply(scene: dict, rows: torch.Tensor, n: int, *, quats_xyzw: bool) -> torch.Tensor:
+    """The float PLY's vertex rows of rows[:n] (v3a_splat_export_pack_ply) -> f32 [n, 14 + 3K]."""
+    a = _export_scene(scene, quats_xyzw, "splat_export_pack_ply")
+    _export_list(rows, "rows", n, a.U)
+    out = torch.empty(n, 14 + 3 * a.K, device=rows.device, dtype=f32)
+    if n:
+        a.rows, a.n, a.out_ply = rows.data_ptr(), n, out.data_ptr()
+        L.check(L.load().v3a_splat_export_pack_ply(C.byref(a), _stream()), "v3a_splat_export_pack_ply")
+    return out

@@ -4,3 +4,15 @@ from .trainer import (PARAM_NAMES, PostOptConfig, adjusted_extrinsics, bilagrid_
                       densify_refine, densify_refines_at, densify_resets_at, densify_state, log_columns, mcmc_growth, mcmc_refine, mcmc_refines_at, pose_learning_rate, pose_transforms, post_optimize, random_backgrounds,
                       train_view_order, train_views, view_order)
 from .evaluate import evaluate_views  # noqa: F401
+
+
+def export_splats_from(splats: dict, format: str = "ply", save_to=None, sh_rest: bool = True) -> bytes:
+    """A trainer state (create_splats / post_optimize's `splats`) as a scene file: the reference trainer's save_ply step
+    (simple_trainer.py calls its exporter's export_splats).  `format` is "ply", "splat" or "ply_compressed"; the parameters are
+    read where they are (logs, logits, xyzw quaternions, one harmonics tensor); sh_rest=False writes the DC colour only."""
+    from ..utils.splat_export import export_scene
+    p = dict(splats["params"])
+    p = {k: p[k].detach() for k in PARAM_NAMES}
+    if not sh_rest:
+        p["sh"] = p["sh"][..., :1].contiguous()
+    return export_scene(p, format, save_to, quats_xyzw=True)

@@ -92,6 +92,13 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
                    help="hold the views with index %% K == 0 out of the post-optimisation (the reference's test_every) and evaluate them "
                         "before and after it: PSNR, SSIM, the number of Gaussians and a time per image - with --post_opt_bilateral_grid "
                         "also the colour-corrected cc_psnr - into post_opt_stats.json next to gaussians.ply; 0 = off")
+    g.add_argument("--export_format", type=str, default="", metavar="FMT[,FMT]",
+                   help="extra scene files next to gaussians.ply, packed on the GPU: a comma list of ply_compressed "
+                        "(gaussians.compressed.ply, SuperSplat's 16 bytes per splat) and splat (gaussians.splat, 32 bytes per splat); "
+                        "empty = none")
+    g.add_argument("--export_sh_rest", action="store_true",
+                   help="with --export_format: write the higher-order harmonics into gaussians.compressed.ply too (default: DC colour "
+                        "only, like gaussians.ply)")
     g.add_argument("--lpips_vgg_weights", type=str, default=None, metavar="PATH",
                    help="with --post_opt_eval_every: torchvision's VGG-16 state dict (vgg16-397923af.pth); with --lpips_lin_weights adds "
                         "LPIPS to post_opt_stats.json")
