@@ -16,6 +16,7 @@
 //
 // Integers only in the scans, fixed order everywhere else: results are bit-identical run to run.
 #include "common.h"
+#include "int_scan.h"
 #include "splat_quat.h"
 #include "../../include/vist3a_hip.h"
 
@@ -30,10 +31,6 @@ constexpr int THREADS = 256;
 constexpr int SH_LANES = 16;                       // lanes that move one parent's harmonics rows
 constexpr int KEEP = 0, CLONE = 1, SPLIT = 2, PRUNED = 4;
 constexpr double LOG_1_6 = 0.47000362924573555;    // log(1.6)
-
-bool bad_count(long n) { return n < 0 || n > 0x7fffffffL; }
-long scan_blocks(long U) { return (U + THREADS - 1) / THREADS; }
-unsigned blocks_for(long n) { return (unsigned)((n + THREADS - 1) / THREADS); }
 
 // -------------------------------------------------------------------------------------------------------------- accumulate
 
@@ -69,23 +66,6 @@ struct ClassP {
   int* block_tot;   // [3, nb]: the blocks' totals, then (in place) their exclusive prefix
 };
 
-// exclusive prefix of x over the workgroup (Hillis-Steele on integers), and the workgroup's total
-__device__ __forceinline__ int block_exclusive_scan(int x, int* buf, int& total) {
-  const int tid = threadIdx.x;
-  buf[tid] = x;
-  __syncthreads();
-  for (int off = 1; off < THREADS; off <<= 1) {
-    const int t = tid >= off ? buf[tid - off] : 0;
-    __syncthreads();
-    buf[tid] += t;
-    __syncthreads();
-  }
-  total = buf[THREADS - 1];
-  const int r = buf[tid] - x;
-  __syncthreads();
-  return r;
-}
-
 // the fate byte and the three counts of every parent; a block's exclusive prefix goes to offsets, its totals to block_tot
 __global__ void __launch_bounds__(THREADS) densify_classify_kernel(const ClassP a) {
   __shared__ int buf[THREADS];
@@ -116,7 +96,7 @@ __global__ void __launch_bounds__(THREADS) densify_classify_kernel(const ClassP 
 #pragma unroll
   for (int s = 0; s < 3; ++s) {
     int total;
-    const int ex = block_exclusive_scan(c[s], buf, total);
+    const int ex = block_exclusive_scan<THREADS>(c[s], buf, total);
     if (g < a.U) {
       a.counts[s * a.U + g] = c[s];
       a.offsets[s * a.U + g] = ex;
@@ -125,18 +105,10 @@ __global__ void __launch_bounds__(THREADS) densify_classify_kernel(const ClassP 
   }
 }
 
-// workgroup s: block_tot[s] becomes its exclusive prefix, 256 blocks at a time with a running carry; totals[s] = the sum
+// workgroup s: block_tot[s] becomes its exclusive prefix; totals[s] = the sum
 __global__ void __launch_bounds__(THREADS) densify_block_prefix_kernel(const ClassP a) {
   __shared__ int buf[THREADS];
-  int* T = a.block_tot + (long)blockIdx.x * a.nb;
-  long run = 0;
-  for (long c0 = 0; c0 < a.nb; c0 += THREADS) {
-    const long b = c0 + threadIdx.x;
-    int total;
-    const int ex = block_exclusive_scan(b < a.nb ? T[b] : 0, buf, total);
-    if (b < a.nb) T[b] = (int)(run + ex);
-    run += total;
-  }
+  const long run = block_totals_to_prefix<THREADS>(a.block_tot + (long)blockIdx.x * a.nb, a.nb, buf);
   if (threadIdx.x == 0) a.totals[blockIdx.x] = run;
 }
 
@@ -307,14 +279,14 @@ extern "C" int v3a_densify_accumulate(const float* d_means2d, const int* radii, 
   if (!d_means2d || !radii || !grad2d || !count) return V3A_ERR_ARG;
   if (bad_count(U) || C < 1 || width < 1 || height < 1) return V3A_ERR_SHAPE;
   if (U == 0) return V3A_OK;
-  hipLaunchKernelGGL(densify_accumulate_kernel, dim3(blocks_for(U)), dim3(THREADS), 0, (hipStream_t)stream, d_means2d, radii, U, C,
+  hipLaunchKernelGGL(densify_accumulate_kernel, dim3(blocks_for(U, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, d_means2d, radii, U, C,
                      0.5 * (double)width * (double)C, 0.5 * (double)height * (double)C, grad2d, count);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
 extern "C" long v3a_densify_classify_workspace_bytes(long U) {
   if (bad_count(U)) return V3A_ERR_SHAPE;
-  return ((3 * scan_blocks(U) * (long)sizeof(int) + 7) / 8) * 8;
+  return ((3 * scan_blocks<THREADS>(U) * (long)sizeof(int) + 7) / 8) * 8;
 }
 
 extern "C" int v3a_densify_classify(const v3a_densify_classify_args* a, void* stream) {
@@ -322,10 +294,10 @@ extern "C" int v3a_densify_classify(const v3a_densify_classify_args* a, void* st
   if (bad_count(a->U)) return V3A_ERR_SHAPE;
   if (a->U == 0) return V3A_OK;
   if (!a->grad2d || !a->count || !a->log_scales || !a->logits || !a->fates || !a->counts || !a->offsets || !a->totals) return V3A_ERR_ARG;
-  if (!a->workspace || ((uintptr_t)a->workspace & 7) || a->workspace_bytes < v3a_densify_classify_workspace_bytes(a->U)) return V3A_ERR_WORKSPACE;
+  if (bad_workspace(a->workspace, a->workspace_bytes, v3a_densify_classify_workspace_bytes(a->U))) return V3A_ERR_WORKSPACE;
   ClassP k;
   k.grad2d = a->grad2d; k.count = a->count; k.ls = a->log_scales; k.logits = a->logits;
-  k.U = a->U; k.nb = scan_blocks(a->U);
+  k.U = a->U; k.nb = scan_blocks<THREADS>(a->U);
   k.grow_grad2d = a->grow_grad2d; k.grow_scale3d = a->grow_scale3d; k.prune_opa = a->prune_opa; k.prune_scale3d = a->prune_scale3d;
   k.grow = a->grow; k.prune_big = a->prune_big; k.revised = a->revised_opacity;
   k.fates = a->fates; k.counts = a->counts; k.offsets = a->offsets; k.totals = a->totals;
@@ -362,9 +334,9 @@ extern "C" int v3a_densify_apply(const v3a_densify_apply_args* a, void* stream) 
   k.U = a->U; k.U_out = a->U_out; k.K = a->K;
   k.key = make_key(a->seed, 0u, a->step);   // Key.stream is the sampler's; the children name their streams (4-7) at each draw
   k.revised = a->revised_opacity;
-  hipLaunchKernelGGL(densify_rows_kernel, dim3(blocks_for(k.U)), dim3(THREADS), 0, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(densify_rows_kernel, dim3(blocks_for(k.U, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, k);
   if (hipGetLastError() != hipSuccess) return V3A_ERR_LAUNCH;
-  hipLaunchKernelGGL(densify_sh_kernel, dim3(blocks_for(k.U * SH_LANES)), dim3(THREADS), 0, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(densify_sh_kernel, dim3(blocks_for(k.U * SH_LANES, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, k);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
@@ -372,6 +344,6 @@ extern "C" int v3a_densify_reset_opacity(float* logits, float* m_logits, float* 
   if (!logits || !m_logits || !v_logits) return V3A_ERR_ARG;
   if (bad_count(U) || !(max_opacity > 0.0) || !(max_opacity < 1.0)) return V3A_ERR_SHAPE;
   if (U == 0) return V3A_OK;
-  hipLaunchKernelGGL(densify_reset_kernel, dim3(blocks_for(U)), dim3(THREADS), 0, (hipStream_t)stream, logits, m_logits, v_logits, U, max_opacity);
+  hipLaunchKernelGGL(densify_reset_kernel, dim3(blocks_for(U, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, logits, m_logits, v_logits, U, max_opacity);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

@@ -160,7 +160,6 @@ static __global__ __launch_bounds__(256) void gs_count_kernel(CountP p) {
   if (e < p.CU) p.counts[e] = entry_tile_count(p.radii, p.means2d, e, p.tw, p.th);
 }
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 inline size_t scan_tmp_bytes(long CU) {
   size_t t = 0;

@@ -28,7 +28,7 @@ constexpr int PER_LANE = 4;
 constexpr long BLOCK_ELEMS = (long)THREADS * PER_LANE;   // 1024 consecutive Gaussians per sampler block
 constexpr int MAX_RATIO = 51;                            // gsplat's n_max: binomials up to C(50, k)
 
-#include "philox.h"   // Rand4, philox4x32_10, uniform53, Key, draw, normal_pair, sigmoid64, make_key
+#include "philox.h"   // Rand4, philox4x32_10, uniform53, Key, draw, normal_pair, make_key
 
 // ---------------------------------------------------------------------------------------------------------------- sampler
 
@@ -113,8 +113,6 @@ __global__ void __launch_bounds__(THREADS) mcmc_pick_kernel(const float* __restr
 }
 
 long sample_blocks(long U) { return (U + BLOCK_ELEMS - 1) / BLOCK_ELEMS; }
-
-bool bad_count(long n) { return n < 1 || n > 0x7fffffffL; }
 
 // ------------------------------------------------------------------------------------------------- relocation and growth
 
@@ -238,8 +236,6 @@ __global__ void __launch_bounds__(THREADS) mcmc_noise_kernel(float* __restrict__
   }
 }
 
-unsigned blocks_for(long n) { return (unsigned)((n + THREADS - 1) / THREADS); }
-
 }  // namespace
 
 extern "C" int v3a_mcmc_philox(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
@@ -252,7 +248,7 @@ extern "C" int v3a_mcmc_philox(const uint32_t* counter, const uint32_t* key, uin
 extern "C" double v3a_mcmc_uniform(uint32_t x0, uint32_t x1) { return uniform53(x0, x1); }
 
 extern "C" long v3a_mcmc_sample_workspace_bytes(long U) {
-  if (bad_count(U)) return V3A_ERR_SHAPE;
+  if (U < 1 || bad_count(U)) return V3A_ERR_SHAPE;
   return (2 * sample_blocks(U) + 1) * (long)sizeof(double);
 }
 
@@ -260,8 +256,8 @@ extern "C" int v3a_mcmc_sample(const float* weights, long U, float min_weight, i
                                unsigned int rng_stream, unsigned int step, int* src, int* counts, void* workspace, long workspace_bytes,
                                void* stream) {
   if (!weights || !src || !counts) return V3A_ERR_ARG;
-  if (bad_count(U) || bad_count(n_slots) || (alive_only && n_slots != U)) return V3A_ERR_SHAPE;
-  if (!workspace || ((uintptr_t)workspace & 7) || workspace_bytes < v3a_mcmc_sample_workspace_bytes(U)) return V3A_ERR_WORKSPACE;
+  if (U < 1 || bad_count(U) || n_slots < 1 || bad_count(n_slots) || (alive_only && n_slots != U)) return V3A_ERR_SHAPE;
+  if (bad_workspace(workspace, workspace_bytes, v3a_mcmc_sample_workspace_bytes(U))) return V3A_ERR_WORKSPACE;
   const long nb = sample_blocks(U);
   double* T = (double*)workspace;
   double* P = T + nb;
@@ -271,13 +267,13 @@ extern "C" int v3a_mcmc_sample(const float* weights, long U, float min_weight, i
   if (hipGetLastError() != hipSuccess) return V3A_ERR_LAUNCH;
   hipLaunchKernelGGL(mcmc_prefix_kernel, dim3(1), dim3(THREADS), 0, (hipStream_t)stream, T, nb, P, total);
   if (hipGetLastError() != hipSuccess) return V3A_ERR_LAUNCH;
-  hipLaunchKernelGGL(mcmc_pick_kernel, dim3(blocks_for(n_slots)), dim3(THREADS), 0, (hipStream_t)stream, weights, U, min_weight, alive_only,
+  hipLaunchKernelGGL(mcmc_pick_kernel, dim3(blocks_for(n_slots, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, weights, U, min_weight, alive_only,
                      n_slots, key, T, P, total, nb, src, counts);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
 extern "C" long v3a_mcmc_relocate_workspace_bytes(long U) {
-  if (bad_count(U)) return V3A_ERR_SHAPE;
+  if (U < 1 || bad_count(U)) return V3A_ERR_SHAPE;
   return U * 4 * (long)sizeof(float);
 }
 
@@ -288,11 +284,11 @@ extern "C" int v3a_mcmc_relocate(const v3a_mcmc_relocate_args* a, void* stream) 
   float* const v[5] = {a->v_means, a->v_log_scales, a->v_quats, a->v_logits, a->v_sh};
   for (int f = 0; f < 5; ++f)
     if (!p[f] || !m[f] || !v[f]) return V3A_ERR_ARG;
-  if (bad_count(a->U) || bad_count(a->n_slots) || a->K < 1 || a->K > 1024) return V3A_ERR_SHAPE;
+  if (a->U < 1 || bad_count(a->U) || a->n_slots < 1 || bad_count(a->n_slots) || a->K < 1 || a->K > 1024) return V3A_ERR_SHAPE;
   if (a->dst_offset == 0 ? a->n_slots != a->U : a->dst_offset != a->U) return V3A_ERR_SHAPE;   // relocation : growth
   if (a->dst_offset + a->n_slots > 0x7fffffffL) return V3A_ERR_SHAPE;
   if (!(a->min_opacity > 0.0) || !(a->min_opacity < 1.0)) return V3A_ERR_SHAPE;
-  if (!a->workspace || ((uintptr_t)a->workspace & 7) || a->workspace_bytes < v3a_mcmc_relocate_workspace_bytes(a->U)) return V3A_ERR_WORKSPACE;
+  if (bad_workspace(a->workspace, a->workspace_bytes, v3a_mcmc_relocate_workspace_bytes(a->U))) return V3A_ERR_WORKSPACE;
   MoveP k;
   k.src = a->src; k.counts = a->counts;
   const int width[5] = {3, 3, 4, 1, 3 * a->K};
@@ -300,17 +296,17 @@ extern "C" int v3a_mcmc_relocate(const v3a_mcmc_relocate_args* a, void* stream) 
   k.U = a->U; k.n_slots = a->n_slots; k.dst_offset = a->dst_offset;
   k.min_opacity = a->min_opacity;
   k.scratch = (float*)a->workspace;
-  hipLaunchKernelGGL(mcmc_new_values_kernel, dim3(blocks_for(k.U)), dim3(THREADS), 0, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(mcmc_new_values_kernel, dim3(blocks_for(k.U, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, k);
   if (hipGetLastError() != hipSuccess) return V3A_ERR_LAUNCH;
-  hipLaunchKernelGGL(mcmc_move_kernel, dim3(blocks_for(k.U + k.n_slots)), dim3(THREADS), 0, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(mcmc_move_kernel, dim3(blocks_for(k.U + k.n_slots, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, k);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
 extern "C" int v3a_mcmc_noise(float* means, const float* log_scales, const float* quats, const float* logits, long U, double scaler,
                               unsigned long long seed, unsigned int step, void* stream) {
   if (!means || !log_scales || !quats || !logits) return V3A_ERR_ARG;
-  if (bad_count(U)) return V3A_ERR_SHAPE;
-  hipLaunchKernelGGL(mcmc_noise_kernel, dim3(blocks_for(U)), dim3(THREADS), 0, (hipStream_t)stream, means, log_scales, quats, logits, U,
+  if (U < 1 || bad_count(U)) return V3A_ERR_SHAPE;
+  hipLaunchKernelGGL(mcmc_noise_kernel, dim3(blocks_for(U, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, means, log_scales, quats, logits, U,
                      scaler, make_key(seed, 0u, step), ((uintptr_t)quats & 15) ? 0 : 1);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

@@ -1,6 +1,7 @@
 // The counter-based random numbers of the post-optimisation strategies: Philox4x32-10, its 53-bit uniforms and Box-Muller normals.
 // One definition behind mcmc.hip and densify.hip (and v3a_mcmc_philox / v3a_mcmc_uniform, the host's known-answer entry points).
 // Include it inside the file's anonymous namespace, AFTER its `#pragma clang fp contract(off)`: nothing here may be contracted.
+// Random numbers only: the opacity both files draw against (sigmoid64) is in splat_quat.h.
 #pragma once
 
 struct Rand4 { uint32_t x[4]; };
@@ -43,8 +44,6 @@ __device__ __forceinline__ void normal_pair(const Rand4& r, double& z0, double& 
   z0 = rad * cospi(2.0 * u2);
   z1 = rad * sinpi(2.0 * u2);
 }
-
-__device__ __forceinline__ double sigmoid64(float x) { return 1.0 / (1.0 + exp(-(double)x)); }
 
 inline Key make_key(unsigned long long seed, unsigned int stream, unsigned int step) {
   Key k;

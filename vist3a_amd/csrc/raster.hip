@@ -203,7 +203,7 @@ struct RLayout { size_t counts, incl, keys0, keys1, vals0, vals1, offs, tmp, tmp
 RLayout rlayout(long CU, long nt_all, long cap) {
   RLayout l{};
   size_t off = 0;
-  auto take = [&](size_t b) { size_t o = off; off += al256(b); return o; };
+  auto take = [&](size_t b) { size_t o = off; off += align256(b); return o; };
   l.counts = take(4 * (size_t)CU); l.incl = take(4 * (size_t)CU);
   l.keys0 = take(8 * (size_t)cap); l.keys1 = take(8 * (size_t)cap);
   l.vals0 = take(4 * (size_t)cap); l.vals1 = take(4 * (size_t)cap);

@@ -228,7 +228,7 @@ struct BLayout { size_t counts, incl, rows, tmp, tmp_bytes, total; };
 BLayout blayout(long CU, long cap) {
   BLayout l{};
   size_t off = 0;
-  auto take = [&](size_t b) { size_t o = off; off += al256(b); return o; };
+  auto take = [&](size_t b) { size_t o = off; off += align256(b); return o; };
   l.counts = take(4 * (size_t)CU); l.incl = take(4 * (size_t)CU);
   l.rows = take(sizeof(float) * ROWF * (size_t)cap);
   l.tmp_bytes = scan_tmp_bytes(CU);

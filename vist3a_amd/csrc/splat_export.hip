@@ -16,6 +16,7 @@
 // Every product-then-sum of the reference is two rounded fp32 operations and every division an IEEE division: contraction is off
 // for the whole file, and the divisions are spelled __fdiv_rn.  expf / sqrtf are the device library's (within 1 ulp).
 #include "common.h"
+#include "int_scan.h"
 #include "../../include/vist3a_hip.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -35,10 +36,6 @@ struct Scene {
   int K, xyzw;
 };
 
-bool bad_count(long n) { return n < 0 || n > 0x7fffffffL; }
-long blocks_of(long n) { return (n + THREADS - 1) / THREADS; }
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 __device__ __forceinline__ bool finite32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ float sigmoid32(float x) { return __fdiv_rn(1.0f, 1.0f + expf(-x)); }
 __device__ __forceinline__ float dc_colour(float sh0) { return sh0 * SH_C0 + 0.5f; }   // sh2rgb: a product, then a sum
@@ -50,23 +47,6 @@ __device__ __forceinline__ void load_quat(const Scene& s, long r, float* q) {
   else { q[0] = p[0]; q[1] = p[1]; q[2] = p[2]; q[3] = p[3]; }
 }
 __device__ __forceinline__ float quat_norm(const float* q) { return sqrtf(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]); }
-
-// exclusive prefix of x over the workgroup (Hillis-Steele on integers), and the workgroup's total
-__device__ __forceinline__ int block_exclusive_scan(int x, int* buf, int& total) {
-  const int tid = threadIdx.x;
-  buf[tid] = x;
-  __syncthreads();
-  for (int off = 1; off < THREADS; off <<= 1) {
-    const int t = tid >= off ? buf[tid - off] : 0;
-    __syncthreads();
-    buf[tid] += t;
-    __syncthreads();
-  }
-  total = buf[THREADS - 1];
-  const int r = buf[tid] - x;
-  __syncthreads();
-  return r;
-}
 
 // ------------------------------------------------------------------------------------------------------------------ filter
 
@@ -107,21 +87,14 @@ __global__ void __launch_bounds__(THREADS) export_flags_kernel(const FilterP a) 
     a.flag[g] = (unsigned char)keep;
   }
   int total;
-  block_exclusive_scan(keep, buf, total);
+  block_exclusive_scan<THREADS>(keep, buf, total);
   if (threadIdx.x == 0) a.block_tot[blockIdx.x] = total;
 }
 
-// one workgroup: block_tot becomes its exclusive prefix, 256 blocks at a time with a running carry; *count = the sum
+// one workgroup: block_tot becomes its exclusive prefix; *count = the sum
 __global__ void __launch_bounds__(THREADS) export_block_prefix_kernel(const FilterP a) {
   __shared__ int buf[THREADS];
-  long run = 0;
-  for (long c0 = 0; c0 < a.nb; c0 += THREADS) {
-    const long b = c0 + threadIdx.x;
-    int total;
-    const int ex = block_exclusive_scan(b < a.nb ? a.block_tot[b] : 0, buf, total);
-    if (b < a.nb) a.block_tot[b] = (int)(run + ex);
-    run += total;
-  }
+  const long run = block_totals_to_prefix<THREADS>(a.block_tot, a.nb, buf);
   if (threadIdx.x == 0) *a.count = run;
 }
 
@@ -130,7 +103,7 @@ __global__ void __launch_bounds__(THREADS) export_scatter_kernel(const FilterP a
   const long g = (long)blockIdx.x * THREADS + threadIdx.x;
   const int keep = g < a.s.U ? a.flag[g] : 0;
   int total;
-  const int ex = block_exclusive_scan(keep, buf, total);
+  const int ex = block_exclusive_scan<THREADS>(keep, buf, total);
   if (keep) a.rows[a.block_tot[blockIdx.x] + ex] = (int)g;
 }
 
@@ -405,7 +378,7 @@ int list_of(const v3a_splat_export_args* a, const int* list) {
 
 extern "C" long v3a_splat_export_filter_workspace_bytes(long U, int K) {
   if (bad_count(U) || K < 0 || K > 1024) return V3A_ERR_SHAPE;
-  return (long)(align256((size_t)U) + align256((size_t)blocks_of(U) * sizeof(int)));
+  return (long)(align256((size_t)U) + align256((size_t)scan_blocks<THREADS>(U) * sizeof(int)));
 }
 
 extern "C" int v3a_splat_export_filter(const v3a_splat_export_args* a, void* stream_) {
@@ -416,13 +389,13 @@ extern "C" int v3a_splat_export_filter(const v3a_splat_export_args* a, void* str
   hipStream_t stream = (hipStream_t)stream_;
   if (a->U == 0) return hipMemsetAsync(a->count, 0, sizeof(long), stream) == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
   if (!a->rows) return V3A_ERR_ARG;
-  if (!a->workspace || ((uintptr_t)a->workspace & 7) || a->workspace_bytes < v3a_splat_export_filter_workspace_bytes(a->U, a->K)) return V3A_ERR_WORKSPACE;
+  if (bad_workspace(a->workspace, a->workspace_bytes, v3a_splat_export_filter_workspace_bytes(a->U, a->K))) return V3A_ERR_WORKSPACE;
   FilterP k;
   k.s = s;
   k.by_opacity = a->filter_opacity != 0; k.threshold = a->opacity_threshold;
   k.flag = (unsigned char*)a->workspace;
   k.block_tot = (int*)((char*)a->workspace + align256((size_t)a->U));
-  k.nb = blocks_of(a->U);
+  k.nb = scan_blocks<THREADS>(a->U);
   k.rows = a->rows; k.count = a->count;
   hipLaunchKernelGGL(export_flags_kernel, dim3((unsigned)k.nb), dim3(THREADS), 0, stream, k);
   if (hipGetLastError() != hipSuccess) return V3A_ERR_LAUNCH;
@@ -445,14 +418,14 @@ extern "C" int v3a_splat_export_sort(const v3a_splat_export_args* a, void* strea
   if (a->n == 0) return V3A_OK;
   if (!a->order) return V3A_ERR_ARG;
   const SortLayout l = sort_layout(a->U);
-  if (!a->workspace || ((uintptr_t)a->workspace & 7) || a->workspace_bytes < (long)l.total) return V3A_ERR_WORKSPACE;
+  if (bad_workspace(a->workspace, a->workspace_bytes, (long)l.total)) return V3A_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)a->workspace;
   SortP k;
   k.s = s;
   k.rows = a->rows; k.n = a->n;
   k.part = (float*)(ws + l.part);
-  const long nb = blocks_of(a->n);
+  const long nb = blocks_for(a->n, THREADS);
   k.nparts = (int)(nb < RANGE_BLOCKS ? nb : RANGE_BLOCKS);
   k.key = (unsigned int*)(ws + l.key_in);
   hipLaunchKernelGGL(export_range_kernel, dim3((unsigned)k.nparts), dim3(THREADS), 0, stream, k);
@@ -479,7 +452,7 @@ extern "C" int v3a_splat_export_pack_compressed(const v3a_splat_export_args* a, 
   PackP k{};
   k.s = s; k.order = a->order; k.n = a->n;
   k.chunks = a->out_chunks; k.vertices = (u32x4*)a->out_vertices; k.shbytes = a->out_sh;
-  hipLaunchKernelGGL(export_compressed_kernel, dim3((unsigned)((a->n + CHUNK - 1) / CHUNK)), dim3(THREADS), 0, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(export_compressed_kernel, dim3(blocks_for(a->n, CHUNK)), dim3(THREADS), 0, (hipStream_t)stream, k);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
@@ -494,7 +467,7 @@ extern "C" int v3a_splat_export_pack_splat(const v3a_splat_export_args* a, void*
   PackP k{};
   k.s = s; k.order = a->order; k.n = a->n;
   k.splat = (u32x4*)a->out_splat;
-  hipLaunchKernelGGL(export_splat_kernel, dim3((unsigned)blocks_of(a->n)), dim3(THREADS), 0, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(export_splat_kernel, dim3(blocks_for(a->n, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, k);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
@@ -506,10 +479,10 @@ extern "C" int v3a_splat_export_pack_ply(const v3a_splat_export_args* a, void* s
   if (a->n == 0) return V3A_OK;
   if (!a->out_ply) return V3A_ERR_ARG;
   const long total = a->n * (14 + 3L * a->K);
-  if (((uintptr_t)a->out_ply & 3) || blocks_of(total) > 0x7fffffffL) return V3A_ERR_SHAPE;
+  if (((uintptr_t)a->out_ply & 3) || blocks_for(total, THREADS) > 0x7fffffffL) return V3A_ERR_SHAPE;
   PackP k{};
   k.s = s; k.order = a->rows; k.n = a->n;
   k.ply = a->out_ply;
-  hipLaunchKernelGGL(export_ply_kernel, dim3((unsigned)blocks_of(total)), dim3(THREADS), 0, (hipStream_t)stream, k);
+  hipLaunchKernelGGL(export_ply_kernel, dim3(blocks_for(total, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, k);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

@@ -13,6 +13,7 @@
 // HBM-bound: 16 bytes read per Gaussian forward, 16 read and 16 written backward.
 #include "common.h"
 #include "fixed_sum.h"
+#include "splat_quat.h"   // sigmoid64
 #include "../../include/vist3a_hip.h"
 
 #pragma clang fp contract(off)
@@ -27,8 +28,6 @@ struct RegP {
   long n_op, n_sc;                    // U and 3 U
   long vec_op, vec_sc;                // 4-element groups of each array moved by 16-byte accesses (0 where a pointer is not aligned)
 };
-
-__device__ __forceinline__ double sigmoid64(float x) { return 1.0 / (1.0 + exp(-(double)x)); }
 
 __global__ void __launch_bounds__(THREADS) splat_reg_fwd_kernel(const RegP p, double* part) {
   __shared__ double red[THREADS];

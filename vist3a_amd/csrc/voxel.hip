@@ -240,8 +240,6 @@ __global__ __launch_bounds__(256) void fuse_combine_kernel(const CombP p) {
   }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 struct Layout {
   size_t key_in, key_out, idx_in, idx_out, head, vid, start, spill, tmp, tmp_bytes, total;
 };

@@ -306,12 +306,14 @@ class AdamArgs(C.Structure):
     ]
 
 
+# the C field names of a scene's five tensors, in the order of ops.SPLAT_TENSORS
+SPLAT_FIELDS = ("means", "log_scales", "quats", "logits", "sh")
+
+
 class McmcRelocateArgs(C.Structure):
     _fields_ = [
         ("src", C.c_void_p), ("counts", C.c_void_p),
-        ("means", C.c_void_p), ("log_scales", C.c_void_p), ("quats", C.c_void_p), ("logits", C.c_void_p), ("sh", C.c_void_p),
-        ("m_means", C.c_void_p), ("m_log_scales", C.c_void_p), ("m_quats", C.c_void_p), ("m_logits", C.c_void_p), ("m_sh", C.c_void_p),
-        ("v_means", C.c_void_p), ("v_log_scales", C.c_void_p), ("v_quats", C.c_void_p), ("v_logits", C.c_void_p), ("v_sh", C.c_void_p),
+        *[(pre + f, C.c_void_p) for pre in ("", "m_", "v_") for f in SPLAT_FIELDS],
         ("U", C.c_long), ("n_slots", C.c_long), ("dst_offset", C.c_long),
         ("K", C.c_int),
         ("min_opacity", C.c_double),
@@ -330,12 +332,9 @@ class DensifyClassifyArgs(C.Structure):
     ]
 
 
-_DENSIFY_FIELDS = ("means", "log_scales", "quats", "logits", "sh")
-
-
 class DensifyApplyArgs(C.Structure):
     _fields_ = (
-        [(pre + f, C.c_void_p) for pre in ("", "m_", "v_", "new_", "new_m_", "new_v_") for f in _DENSIFY_FIELDS]
+        [(pre + f, C.c_void_p) for pre in ("", "m_", "v_", "new_", "new_m_", "new_v_") for f in SPLAT_FIELDS]
         + [("fates", C.c_void_p), ("offsets", C.c_void_p), ("totals", C.c_void_p),
            ("U", C.c_long), ("U_out", C.c_long),
            ("K", C.c_int),
@@ -346,8 +345,8 @@ class DensifyApplyArgs(C.Structure):
 
 class SplatExportArgs(C.Structure):
     _fields_ = (
-        [(f, C.c_void_p) for f in _DENSIFY_FIELDS]
-        + [("ld_" + f, C.c_long) for f in _DENSIFY_FIELDS]
+        [(f, C.c_void_p) for f in SPLAT_FIELDS]
+        + [("ld_" + f, C.c_long) for f in SPLAT_FIELDS]
         + [("U", C.c_long), ("K", C.c_int), ("quats_xyzw", C.c_int),
            ("filter_opacity", C.c_int), ("opacity_threshold", C.c_float),
            ("rows", C.c_void_p), ("count", C.c_void_p), ("n", C.c_long), ("order", C.c_void_p),

@@ -1884,7 +1884,20 @@ def mcmc_sample(weights: torch.Tensor, *, min_weight: float, alive_only: bool, n
     return src, counts
 
 
-_MCMC_TENSORS = ("means", "scales", "quats", "opacities", "sh")
+SPLAT_TENSORS = ("means", "scales", "quats", "opacities", "sh")   # a scene's five tensors, in the order of lib.SPLAT_FIELDS
+
+
+def _splat_dicts(what: str, params: dict, m: dict, v: dict, rows: int) -> int:
+    """`params`, `m` and `v` each hold the five SPLAT_TENSORS as contiguous f32 device tensors of `rows` rows -> K of sh [rows,3,K]"""
+    sh = params["sh"]
+    if sh.dim() != 3 or sh.shape[1] != 3 or sh.shape[2] < 1:
+        raise ValueError(f"{what}: sh must be [rows,3,K], got {tuple(sh.shape)}")
+    K = sh.shape[2]
+    shapes = dict(means=(rows, 3), scales=(rows, 3), quats=(rows, 4), opacities=(rows,), sh=(rows, 3, K))
+    for group, d in (("params", params), ("m", m), ("v", v)):
+        for name in SPLAT_TENSORS:
+            _f32_dev(d[name], f"{group}[{name!r}]", shapes[name])
+    return K
 
 
 def mcmc_relocate(src: torch.Tensor, counts: torch.Tensor, params: dict, m: dict, v: dict, *, dst_offset: int, min_opacity: float) -> None:
@@ -1901,19 +1914,12 @@ def mcmc_relocate(src: torch.Tensor, counts: torch.Tensor, params: dict, m: dict
     for name, t in (("src", src), ("counts", counts)):
         if not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous():
             raise ValueError(f"mcmc_relocate: {name} must be a contiguous int32 device vector, got {t.dtype} {tuple(t.shape)} on {t.device}")
-    sh = params["sh"]
-    if sh.dim() != 3 or sh.shape[1] != 3 or sh.shape[2] < 1:
-        raise ValueError(f"mcmc_relocate: sh must be [rows,3,K], got {tuple(sh.shape)}")
-    K = sh.shape[2]
-    shapes = dict(means=(rows, 3), scales=(rows, 3), quats=(rows, 4), opacities=(rows,), sh=(rows, 3, K))
-    for group, d in (("params", params), ("m", m), ("v", v)):
-        for name in _MCMC_TENSORS:
-            _f32_dev(d[name], f"{group}[{name!r}]", shapes[name])
+    K = _splat_dicts("mcmc_relocate", params, m, v, rows)
     if not 0.0 < float(min_opacity) < 1.0:
         raise ValueError(f"mcmc_relocate: min_opacity must lie in (0, 1), got {min_opacity!r}")
     lib = L.load()
     ws, ws_bytes = _workspace(lib.v3a_mcmc_relocate_workspace_bytes(U), f"v3a_mcmc_relocate_workspace_bytes (U = {U})", src.device)
-    a = L.McmcRelocateArgs(_ptr(src), _ptr(counts), *(_ptr(d[name]) for d in (params, m, v) for name in _MCMC_TENSORS), U, n, dst_offset, K,
+    a = L.McmcRelocateArgs(_ptr(src), _ptr(counts), *(_ptr(d[name]) for d in (params, m, v) for name in SPLAT_TENSORS), U, n, dst_offset, K,
                            float(min_opacity), _ptr(ws), ws_bytes)
     L.check(lib.v3a_mcmc_relocate(C.byref(a), _stream()), "v3a_mcmc_relocate")
 
@@ -2000,14 +2006,7 @@ def densify_apply(cls: dict, params: dict, m: dict, v: dict, *, seed: int, step:
     states a child's values).  The old tensors are read only.  `totals` = cls["totals"].tolist() if the caller has read it already;
     otherwise it is read here: the refine's one read-back, which sizes the new tensors."""
     U = cls["fates"].shape[0]
-    sh = params["sh"]
-    if sh.dim() != 3 or sh.shape[1] != 3 or sh.shape[2] < 1:
-        raise ValueError(f"densify_apply: sh must be [U,3,K], got {tuple(sh.shape)}")
-    K = sh.shape[2]
-    shapes = dict(means=(U, 3), scales=(U, 3), quats=(U, 4), opacities=(U,), sh=(U, 3, K))
-    for group, d in (("params", params), ("m", m), ("v", v)):
-        for name in _MCMC_TENSORS:
-            _f32_dev(d[name], f"{group}[{name!r}]", shapes[name])
+    K = _splat_dicts("densify_apply", params, m, v, U)
     if cls["fates"].dtype != torch.uint8 or not cls["fates"].is_cuda or not cls["fates"].is_contiguous():
         raise ValueError("densify_apply: cls['fates'] must be a contiguous uint8 device vector")
     _i32_dev(cls["offsets"], "cls['offsets']", (3, U))
@@ -2018,11 +2017,11 @@ def densify_apply(cls: dict, params: dict, m: dict, v: dict, *, seed: int, step:
     U_out = nA + nB + 2 * nC
     if min(nA, nB, nC) < 0 or nA + nB > 2 * U or nC > U or U_out >= 2 ** 31:
         raise ValueError(f"densify_apply: segment totals {(nA, nB, nC)} do not belong to {U} Gaussians")
-    dev = sh.device
-    new = [{name: torch.empty((U_out,) + shapes[name][1:], device=dev, dtype=f32) for name in _MCMC_TENSORS} for _ in range(3)]
+    dev = params["sh"].device
+    new = [{name: torch.empty((U_out,) + tuple(params[name].shape[1:]), device=dev, dtype=f32) for name in SPLAT_TENSORS} for _ in range(3)]
     if U == 0 or U_out == 0:
         return tuple(new)
-    a = L.DensifyApplyArgs(*(_ptr(d[name]) for d in (params, m, v, *new) for name in _MCMC_TENSORS), _ptr(cls["fates"]), _ptr(cls["offsets"]),
+    a = L.DensifyApplyArgs(*(_ptr(d[name]) for d in (params, m, v, *new) for name in SPLAT_TENSORS), _ptr(cls["fates"]), _ptr(cls["offsets"]),
                            _ptr(cls["totals"]), U, U_out, K, seed, step, int(bool(revised_opacity)))
     L.check(L.load().v3a_densify_apply(C.byref(a), _stream()), "v3a_densify_apply")
     return tuple(new)
@@ -2053,7 +2052,7 @@ def _export_scene(scene: dict, quats_xyzw: bool, what: str) -> L.SplatExportArgs
     U, K = means.shape[0], sh.shape[2] - 1
     inner = dict(means=(3,), scales=(3,), quats=(4,), opacities=(), sh=(3, K + 1))
     a = L.SplatExportArgs()
-    for field, name in zip(L._DENSIFY_FIELDS, _MCMC_TENSORS):
+    for field, name in zip(L.SPLAT_FIELDS, SPLAT_TENSORS):
         t = scene[name]
         if not t.is_cuda or t.dtype != f32:
             raise ValueError(f"{what}: {name} must be a float32 device tensor (the HIP path has no CPU fallback), got {t.dtype} on {t.device}")

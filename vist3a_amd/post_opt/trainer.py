@@ -57,7 +57,7 @@ import torch
 from .. import ops
 from ..models.types import Gaussians
 
-PARAM_NAMES = ("means", "scales", "quats", "opacities", "sh")   # "sh" = the reference's sh0 and shN
+PARAM_NAMES = ops.SPLAT_TENSORS   # "sh" = the reference's sh0 and shN
 
 
 @dataclass
