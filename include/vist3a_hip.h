@@ -1010,6 +1010,54 @@ int v3a_splat_export_pack_compressed(const v3a_splat_export_args* a, void* strea
 int v3a_splat_export_pack_splat(const v3a_splat_export_args* a, void* stream);
 int v3a_splat_export_pack_ply(const v3a_splat_export_args* a, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Scene import decoded on the device (csrc/splat_import.hip): the three files above read back into the trainer's storage.
+ * DESIGN.md section 7h states the decoding.  All three entry points take one struct.
+ *
+ * Outputs (the export kernels' inputs): means f32 [n,3], log-scales f32 [n,3], quaternions f32 [n,4] (quats_xyzw != 0: stored
+ * x y z w; else w x y z, the files' order), opacity logits f32 [n], harmonics f32 [n,3,K+1], K = n_rest / 3, coefficient 0 the
+ * DC term (f_rest_j, j = c K + k, is sh[u][c][1+k]).  ld_*: row strides in ELEMENTS (>= 3, 3, 4, 1, 3 (K+1)).  Every output
+ * element is written exactly once with plain stores; nothing else is written but the workspace.  bad int32 [1] on the DEVICE:
+ * the number of rows with a NaN or Inf among their outputs (per-workgroup integer totals in the workspace, summed by one
+ * workgroup: no memset, no atomics).
+ * Input: `payload`, the file's bytes after the text header, on the device, 4-byte aligned (V3A_ERR_SHAPE otherwise); nothing
+ * outside [payload, payload + payload_bytes) is read.  fp32 throughout, no contraction, IEEE divisions; logf / sqrtf are the
+ * device library's.
+ *
+ * v3a_splat_import_ply: rows of P floats; offsets[15] = the columns of x y z, f_dc_0..2, f_rest_0 (f_rest_j at f_rest_0 + j),
+ *   opacity, scale_0..2, rot_0..3 (w x y z), all distinct and < P <= 4096; other columns are skipped.  Values are copied;
+ *   opacity_linear != 0: logit = logf(o / (1 - o)) of o = the value clamped to [1e-6, 1 - 1e-6] (a NaN stays one).
+ *   payload_bytes == 4 n P.
+ * v3a_splat_import_compressed: nch == ceil(n / 256) chunks of 18 floats, n vertices of 4 words, n x n_rest bytes;
+ *   payload_bytes == 72 nch + 16 n + n n_rest.  Position and log-scale lo + (hi - lo) * (code / top), top = 2047, 1023, 2047;
+ *   sh0 = ((lo + (hi - lo) * (code / 255)) - 0.5) / 0.28209479; f_rest = ((byte + 0.5) / 256 - 0.5) * 8; logit =
+ *   logf(c / (255 - c)), c = clamp(code, 0.5, 254.5); rotation v = (code / 1023 - 0.5) * sqrt(2), the dropped component
+ *   sqrtf(max(0, 1 - sum v^2)) at the index in bits 31:30 (w x y z numbering), the others in ascending order.
+ * v3a_splat_import_splat: n records of 32 bytes, n_rest == 0, payload_bytes == 32 n: means copied, logf(scale),
+ *   sh0 = ((b + 0.5) / 255 - 0.5) / 0.28209479, logit as above with c = clamp(b + 0.5, 0.5, 254.5), rotation
+ *   (b + 0.5 - 128) / 128 (w x y z, not renormalised).
+ * Refusals, before any pointer is read: a null struct or (n > 0) a null pointer V3A_ERR_ARG; n < 0 or >= 2^31, n_rest < 0,
+ *   n_rest % 3 != 0, n_rest / 3 > 63, an offset >= P or repeated, a row stride too small, a payload size that disagrees
+ *   V3A_ERR_SHAPE; workspace smaller than v3a_splat_import_workspace_bytes(n) or not 8-byte aligned V3A_ERR_WORKSPACE.
+ *   n == 0 launches nothing (and leaves *bad alone).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  float *means, *log_scales, *quats, *logits, *sh;
+  long ld_means, ld_log_scales, ld_quats, ld_logits, ld_sh;
+  long n;
+  int n_rest, quats_xyzw;
+  int* bad;
+  const unsigned char* payload; long payload_bytes;
+  long nch;                                    /* compressed */
+  int opacity_linear, P;                       /* ply */
+  int offsets[15];                             /* ply */
+  void* workspace; long workspace_bytes;
+} v3a_splat_import_args;
+long v3a_splat_import_workspace_bytes(long n);   /* V3A_ERR_SHAPE for n < 0 or n >= 2^31 */
+int v3a_splat_import_ply(const v3a_splat_import_args* a, void* stream);
+int v3a_splat_import_compressed(const v3a_splat_import_args* a, void* stream);
+int v3a_splat_import_splat(const v3a_splat_import_args* a, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

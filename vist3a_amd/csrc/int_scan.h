@@ -1,8 +1,9 @@
 // The one integer scan behind the stream compactions of the post-optimisation and export kernels: the three segment offsets of
 // v3a_densify_classify (densify.hip) and the survivor list of v3a_splat_export_filter (splat_export.hip).  Both cut their rows
 // into blocks of THREADS, scan every block, and let one workgroup turn the blocks' totals into their exclusive prefix.
+// splat_import.hip uses the second stage alone: the sum of its workgroups' counts of non-finite rows.
 // tests/test_int_scan_gpu.py pins offsets and totals through both users at one row, around one block, and around the 256 blocks
-// that one round of the second stage holds.  Included by those two files only, not by common.h.
+// that one round of the second stage holds.  Included by those three files only, not by common.h.
 //
 // Integers only: no order of the additions can change a result, so every user is bit-identical run to run.  The sums are int32;
 // the entry points refuse more than 2^31 - 1 rows.

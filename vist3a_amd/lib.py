@@ -356,6 +356,20 @@ class SplatExportArgs(C.Structure):
     )
 
 
+class SplatImportArgs(C.Structure):
+    _fields_ = (
+        [(f, C.c_void_p) for f in SPLAT_FIELDS]
+        + [("ld_" + f, C.c_long) for f in SPLAT_FIELDS]
+        + [("n", C.c_long), ("n_rest", C.c_int), ("quats_xyzw", C.c_int),
+           ("bad", C.c_void_p),
+           ("payload", C.c_void_p), ("payload_bytes", C.c_long),
+           ("nch", C.c_long),
+           ("opacity_linear", C.c_int), ("P", C.c_int),
+           ("offsets", C.c_int * 15),
+           ("workspace", C.c_void_p), ("workspace_bytes", C.c_long)]
+    )
+
+
 # name -> (restype, argtypes); every symbol include/vist3a_hip.h declares must be listed here
 SYMBOLS = {
     "v3a_abi_version": (C.c_int, []),
@@ -469,10 +483,14 @@ SYMBOLS = {
     "v3a_splat_export_pack_compressed": (C.c_int, [C.POINTER(SplatExportArgs), C.c_void_p]),
     "v3a_splat_export_pack_splat": (C.c_int, [C.POINTER(SplatExportArgs), C.c_void_p]),
     "v3a_splat_export_pack_ply": (C.c_int, [C.POINTER(SplatExportArgs), C.c_void_p]),
+    "v3a_splat_import_workspace_bytes": (C.c_long, [C.c_long]),
+    "v3a_splat_import_ply": (C.c_int, [C.POINTER(SplatImportArgs), C.c_void_p]),
+    "v3a_splat_import_compressed": (C.c_int, [C.POINTER(SplatImportArgs), C.c_void_p]),
+    "v3a_splat_import_splat": (C.c_int, [C.POINTER(SplatImportArgs), C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 34  # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 35  # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

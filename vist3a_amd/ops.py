@@ -2143,3 +2143,82 @@ def splat_export_pack_ply(scene: dict, rows: torch.Tensor, n: int, *, quats_xyzw
         a.rows, a.n, a.out_ply = rows.data_ptr(), n, out.data_ptr()
         L.check(L.load().v3a_splat_export_pack_ply(C.byref(a), _stream()), "v3a_splat_export_pack_ply")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ scene import (csrc/splat_import.hip)
+PLY_COLUMNS = (("x", "y", "z") + tuple(f"f_dc_{j}" for j in range(3)) + ("f_rest_0", "opacity") + tuple(f"scale_{j}" for j in range(3))
+               + tuple(f"rot_{j}" for j in range(4)))     # the order of v3a_splat_import_args.offsets
+
+
+def _import_outputs(n: int, K: int, dev, out: Optional[dict], what: str):
+    """The five output tensors of a load - fresh, or the caller's (strided rows allowed, as for the exporter) - and the args struct
+    with them, `bad` and the workspace set.  -> (args, scene dict, bad int32 [1], workspace)"""
+    inner = dict(means=(3,), scales=(3,), quats=(4,), opacities=(), sh=(3, K + 1))
+    if out is None:
+        out = {name: torch.empty((n,) + inner[name], device=dev, dtype=f32) for name in SPLAT_TENSORS}
+    a = L.SplatImportArgs()
+    for field, name in zip(L.SPLAT_FIELDS, SPLAT_TENSORS):
+        t = out[name]
+        if not t.is_cuda or t.dtype != f32 or tuple(t.shape) != (n,) + inner[name]:
+            raise ValueError(f"{what}: out[{name!r}] must be a float32 device tensor of shape {(n,) + inner[name]}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        width = 1
+        for w in inner[name]:
+            width *= w
+        if n > 0 and width > 1 and not t[0].is_contiguous():
+            raise ValueError(f"{what}: the elements of a row of out[{name!r}] must be contiguous, got strides {t.stride()}")
+        ld = t.stride(0) if n > 1 else width
+        if ld < width:
+            raise ValueError(f"{what}: rows of out[{name!r}] overlap (row stride {ld} < {width})")
+        setattr(a, field, t.data_ptr())
+        setattr(a, "ld_" + field, ld)
+    bad = torch.zeros(1, device=dev, dtype=torch.int32)
+    ws = None
+    if n > 0:
+        ws, a.workspace_bytes = _workspace(L.load().v3a_splat_import_workspace_bytes(n), f"v3a_splat_import_workspace_bytes (n = {n})", dev)
+        a.workspace = ws.data_ptr()
+    a.n, a.n_rest, a.bad = n, 3 * K, bad.data_ptr()
+    return a, {name: out[name] for name in SPLAT_TENSORS}, bad, ws
+
+
+def _import_payload(payload: torch.Tensor, what: str) -> None:
+    if not payload.is_cuda or payload.dtype != torch.uint8 or payload.dim() != 1 or not payload.is_contiguous():
+        raise ValueError(f"{what}: the payload must be a contiguous uint8 device vector (the HIP path has no CPU fallback), got {payload.dtype} "
+                         f"{tuple(payload.shape)} on {payload.device}")
+
+
+def splat_import_ply(payload: torch.Tensor, n: int, K: int, table: dict, *, opacity: str = "logit", quats_xyzw: bool = True, out: Optional[dict] = None):
+    """The vertex rows of a float PLY (v3a_splat_import_ply): payload uint8 [4 n P] on the device; table = {"P": floats per row,
+    name: column of each of PLY_COLUMNS}.  opacity: "logit" (copied) or "linear" (logit of the value clamped to [1e-6, 1 - 1e-6]).
+    -> (dict(means, scales (logs), quats, opacities (logits), sh [n,3,K+1]), bad int32 [1] on the device: rows with a NaN or Inf)."""
+    if opacity not in ("logit", "linear"):
+        raise ValueError(f"splat_import_ply: opacity must be 'logit' or 'linear', got {opacity!r}")
+    _import_payload(payload, "splat_import_ply")
+    a, scene, bad, ws = _import_outputs(n, K, payload.device, out, "splat_import_ply")
+    if n:
+        a.payload, a.payload_bytes, a.quats_xyzw = payload.data_ptr(), payload.numel(), int(bool(quats_xyzw))
+        a.P, a.opacity_linear = int(table["P"]), int(opacity == "linear")
+        for j, name in enumerate(PLY_COLUMNS):
+            a.offsets[j] = int(table[name]) if K or name != "f_rest_0" else 0      # K = 0: an empty range, it overlaps nothing
+        L.check(L.load().v3a_splat_import_ply(C.byref(a), _stream()), "v3a_splat_import_ply")
+    return scene, bad
+
+
+def splat_import_compressed(payload: torch.Tensor, n: int, K: int, *, quats_xyzw: bool = True, out: Optional[dict] = None):
+    """A compressed PLY's three elements, back to back (v3a_splat_import_compressed): payload uint8 [72 ceil(n/256) + 16 n + 3 K n].
+    -> (scene dict, bad) as splat_import_ply."""
+    _import_payload(payload, "splat_import_compressed")
+    a, scene, bad, ws = _import_outputs(n, K, payload.device, out, "splat_import_compressed")
+    if n:
+        a.payload, a.payload_bytes, a.quats_xyzw, a.nch = payload.data_ptr(), payload.numel(), int(bool(quats_xyzw)), (n + 255) // 256
+        L.check(L.load().v3a_splat_import_compressed(C.byref(a), _stream()), "v3a_splat_import_compressed")
+    return scene, bad
+
+
+def splat_import_splat(payload: torch.Tensor, n: int, *, quats_xyzw: bool = True, out: Optional[dict] = None):
+    """The 32-byte records of a .splat (v3a_splat_import_splat): payload uint8 [32 n].  -> (scene dict with K = 0, bad)."""
+    _import_payload(payload, "splat_import_splat")
+    a, scene, bad, ws = _import_outputs(n, 0, payload.device, out, "splat_import_splat")
+    if n:
+        a.payload, a.payload_bytes, a.quats_xyzw = payload.data_ptr(), payload.numel(), int(bool(quats_xyzw))
+        L.check(L.load().v3a_splat_import_splat(C.byref(a), _stream()), "v3a_splat_import_splat")
+    return scene, bad
