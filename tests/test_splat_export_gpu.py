@@ -133,7 +133,7 @@ def test_guard_bands(hip_lib, fx, U):
     L = hip_lib
     g_in = {k: G.carve_like(v) for k, v in tight.items()}
     a = lib.SplatExportArgs()
-    for field, name in zip(lib.SPLAT_FIELDS, ("means", "scales", "quats", "opacities", "sh")):
+    for field, name in zip(lib.SPLAT_FIELDS, ops.SPLAT_TENSORS):
         setattr(a, field, p(g_in[name]))
     a.ld_means, a.ld_log_scales, a.ld_quats, a.ld_logits, a.ld_sh = 3, 3, 4, 1, 3 * (K + 1)
     a.U, a.K, a.quats_xyzw, a.filter_opacity, a.opacity_threshold = U, K, 0, 1, 1 / 255

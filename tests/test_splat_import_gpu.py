@@ -244,3 +244,55 @@ def test_strides_and_guard_bands(hip_lib, fx, fmt):
     assert G.unchanged(payload, tight_payload)
     with pytest.raises(RuntimeError, match="V3A_ERR_SHAPE"):
         call(payload[:-1])
+
+
+def _wide(t, pad):
+    """t's values in a view whose rows lie `pad` floats further apart than they need to, NaNs between them"""
+    flat = t.reshape(t.shape[0], -1)
+    buf = torch.full((flat.shape[0], flat.shape[1] + pad), float("nan"), device=t.device)
+    buf[:, :flat.shape[1]] = flat
+    return buf[:, 0] if t.dim() == 1 else buf[:, :flat.shape[1]].view(t.shape)
+
+
+def _export_then_import(scene, xyzw, pads):
+    """every format packed from `scene` and decoded again, the decoders' outputs `pads` floats wider than their rows (None: fresh
+    contiguous tensors) -> {format: scene dict}"""
+    from vist3a_amd import ops
+    U, K = scene["means"].shape[0], scene["sh"].shape[2] - 1
+    out = lambda k: None if pads is None else {name: _wide(torch.zeros((U,) + inner, device="cuda"), pad)
+                                               for (name, inner), pad in zip(ops._splat_inner(k + 1).items(), pads)}
+    rows, count = ops.splat_export_filter(scene, quats_xyzw=xyzw)
+    assert int(count.item()) == U
+    order = ops.splat_export_sort(scene, rows, U, quats_xyzw=xyzw)
+    flat = lambda *ts: torch.cat([t.contiguous().view(torch.uint8).reshape(-1) for t in ts])
+    cols = (0, 1, 2, 3, 4, 5, 6) + tuple(6 + 3 * K + j for j in range(8))
+    table = dict(zip(ops.PLY_COLUMNS, cols), P=14 + 3 * K)
+    got = {"ply": ops.splat_import_ply(flat(ops.splat_export_pack_ply(scene, rows, U, quats_xyzw=xyzw)), U, K, table, quats_xyzw=xyzw, out=out(K)),
+           "ply_compressed": ops.splat_import_compressed(flat(*ops.splat_export_pack_compressed(scene, order, U, quats_xyzw=xyzw)), U, K,
+                                                         quats_xyzw=xyzw, out=out(K)),
+           "splat": ops.splat_import_splat(flat(ops.splat_export_pack_splat(scene, order, U, quats_xyzw=xyzw)), U, quats_xyzw=xyzw, out=out(0))}
+    assert all(int(bad.item()) == 0 for _, bad in got.values())
+    return {fmt: s for fmt, (s, _) in got.items()}
+
+
+@pytest.mark.parametrize("xyzw", [False, True])
+@pytest.mark.parametrize("K", [0, 1])
+@pytest.mark.parametrize("U", [1, 257])
+def test_strided_round_trip_equals_the_contiguous_one(hip_lib, U, K, xyzw):
+    """Export then import with every tensor of both a strided view (a different stride above the width for each), against the same
+    round trip through contiguous tensors: bit for bit, in all three formats.  A stride or a field taken from the wrong slot of the
+    kernels' shared view shows here; the float PLY, a copy, must also return the scene itself."""
+    from vist3a_amd import ops
+    assert FIELDS == ops.SPLAT_TENSORS
+    g = torch.Generator().manual_seed(100 * U + 10 * K + xyzw)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    tight = {k: v.cuda() for k, v in dict(means=rn(U, 3), scales=rn(U, 3) * 0.5 - 2, quats=rn(U, 4), opacities=rn(U), sh=rn(U, 3, K + 1)).items()}
+    wide = {k: _wide(v, pad) for (k, v), pad in zip(tight.items(), (2, 1, 3, 1, 5))}
+    assert all(U == 1 or not v.is_contiguous() for v in wide.values())
+    want, got = _export_then_import(tight, xyzw, None), _export_then_import(wide, xyzw, (4, 2, 1, 3, 2))
+    for fmt in SO.FORMATS:
+        for k in FIELDS:
+            assert U == 1 or not got[fmt][k].is_contiguous()
+            assert torch.equal(G.bits(got[fmt][k]), G.bits(want[fmt][k])), (fmt, k)
+    for k in FIELDS:
+        assert torch.equal(G.bits(got["ply"][k]), G.bits(tight[k])), k

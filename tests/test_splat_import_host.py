@@ -2,7 +2,6 @@
 every refusal), the fp32 twin of tests/splat_import_oracle.py against the fp64 decoders of tests/splat_export_oracle.py on every
 fixture file, the ctypes struct against the header's declaration, and the C ABI's refusals (no GPU needed)."""
 import ctypes as C
-import re
 import sys
 from pathlib import Path
 
@@ -13,9 +12,9 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 import splat_export_oracle as SO  # noqa: E402
 import splat_import_oracle as IO  # noqa: E402
+from c_layout import assert_mirrors  # noqa: E402
 
 CASES = tuple(SO.CASES)
-ROOT = Path(__file__).resolve().parents[1]
 
 
 @pytest.fixture(scope="module")
@@ -166,42 +165,10 @@ def test_linear_opacity_twin():
 
 
 # ---------------------------------------------------------------------------------------------------------------- the C ABI
-_SIZES = {"long": 8, "int": 4, "float": 4}
-
-
-def _c_layout(name: str):
-    """{field: (offset, size)} and the total size of the typedef struct `name` in include/vist3a_hip.h (LP64: pointers and longs 8
-    bytes, ints 4, natural alignment)"""
-    txt = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "vist3a_hip.h").read_text(), flags=re.S)
-    body = re.search(r"typedef struct \{([^}]*)\}\s*" + name + r"\s*;", txt).group(1)
-    off, fields, biggest = 0, {}, 1
-    for decl in (d.strip() for d in body.split(";")):
-        if not decl:
-            continue
-        first, *more = [p.strip() for p in decl.split(",")]
-        base = first[:re.search(r"[\w\[\]]+$", first).start()].strip()            # the type in front of the first declarator
-        for d in [first[len(base):].strip()] + more:
-            pointer = d.startswith("*") or base.endswith("*")
-            m = re.fullmatch(r"\*?\s*(\w+)(?:\[(\d+)\])?", d)
-            size = 8 if pointer else _SIZES[base.replace("const", "").replace("unsigned", "").strip() or "int"]
-            count = int(m.group(2) or 1)
-            off = (off + size - 1) // size * size
-            fields[m.group(1)] = (off, size * count)
-            off += size * count
-            biggest = max(biggest, size)
-    return fields, (off + biggest - 1) // biggest * biggest
-
-
 def test_ctypes_struct_matches_the_header():
     from vist3a_amd import lib
-    fields, size = _c_layout("v3a_splat_import_args")
-    assert [f for f, _ in lib.SplatImportArgs._fields_] == list(fields)
-    for f, (off, sz) in fields.items():
-        d = getattr(lib.SplatImportArgs, f)
-        assert (d.offset, d.size) == (off, sz), (f, d.offset, d.size, off, sz)
-    assert C.sizeof(lib.SplatImportArgs) == size
-    fields, size = _c_layout("v3a_splat_export_args")                              # the parser of this test, on a struct known good
-    assert C.sizeof(lib.SplatExportArgs) == size and [f for f, _ in lib.SplatExportArgs._fields_] == list(fields)
+    assert_mirrors(lib.SplatImportArgs, "v3a_splat_import_args")                  # names in order, every (offset, size), sizeof
+    assert_mirrors(lib.SplatExportArgs, "v3a_splat_export_args")
     assert lib.EXPECTED_ABI >= 35
 
 

@@ -18,6 +18,7 @@
 #include "common.h"
 #include "int_scan.h"
 #include "splat_quat.h"
+#include "splat_scene.h"
 #include "../../include/vist3a_hip.h"
 
 // Below this line only (as in mcmc.hip): quat_R<double> is defined above it and may be contracted; the child means are held to 2^-23.
@@ -122,7 +123,7 @@ __global__ void __launch_bounds__(THREADS) densify_offsets_kernel(const ClassP a
 // ------------------------------------------------------------------------------------------------------------------- apply
 
 struct ApplyP {
-  const float* o[15]; float* n[15];   // [group * 5 + field]: group 0 params, 1 m, 2 v; field 0 means, 1 log-scales, 2 quats, 3 logits, 4 sh
+  SplatSet<const float> o[SPLAT_GROUPS]; SplatSet<float> n[SPLAT_GROUPS];   // the old and the new [group][field]
   const unsigned char* fates; const int* offsets; const long* totals;
   long U, U_out;
   int K;
@@ -159,41 +160,40 @@ __global__ void __launch_bounds__(THREADS) densify_rows_kernel(const ApplyP a) {
   long r[2];
   const int n = dest_rows(a, g, fate, r);
   if (n == 0) return;
-  constexpr int width[4] = {3, 3, 4, 1};
-  float p[4][4];
+  float p[SPLAT_SH][4];
 #pragma unroll
-  for (int f = 0; f < 4; ++f)
+  for (int f = 0; f < SPLAT_SH; ++f)
 #pragma unroll
-    for (int e = 0; e < width[f]; ++e) p[f][e] = a.o[f][g * width[f] + e];
+    for (int e = 0, w = splat_width(f, 0); e < w; ++e) p[f][e] = a.o[SPLAT_PARAMS][f][g * w + e];
   if (fate != SPLIT) {
 #pragma unroll
-    for (int f = 0; f < 4; ++f)
+    for (int f = 0; f < SPLAT_SH; ++f)
 #pragma unroll
-      for (int e = 0; e < width[f]; ++e) {
-        a.n[f][r[0] * width[f] + e] = p[f][e];
-        a.n[5 + f][r[0] * width[f] + e] = a.o[5 + f][g * width[f] + e];
-        a.n[10 + f][r[0] * width[f] + e] = a.o[10 + f][g * width[f] + e];
+      for (int e = 0, w = splat_width(f, 0); e < w; ++e) {
+        a.n[SPLAT_PARAMS][f][r[0] * w + e] = p[f][e];
+        a.n[SPLAT_M][f][r[0] * w + e] = a.o[SPLAT_M][f][g * w + e];
+        a.n[SPLAT_V][f][r[0] * w + e] = a.o[SPLAT_V][f][g * w + e];
         if (n == 2) {
-          a.n[f][r[1] * width[f] + e] = p[f][e];
-          a.n[5 + f][r[1] * width[f] + e] = 0.f;
-          a.n[10 + f][r[1] * width[f] + e] = 0.f;
+          a.n[SPLAT_PARAMS][f][r[1] * w + e] = p[f][e];
+          a.n[SPLAT_M][f][r[1] * w + e] = 0.f;
+          a.n[SPLAT_V][f][r[1] * w + e] = 0.f;
         }
       }
     return;
   }
   double q[4], R[9], sc[3];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) q[e] = p[2][e];
+  for (int e = 0; e < 4; ++e) q[e] = p[SPLAT_QUATS][e];
   quat_R<double>(q, R);
   float child_ls[3];
 #pragma unroll
   for (int e = 0; e < 3; ++e) {
-    sc[e] = exp((double)p[1][e]);
-    child_ls[e] = (float)((double)p[1][e] - LOG_1_6);
+    sc[e] = exp((double)p[SPLAT_LS][e]);
+    child_ls[e] = (float)((double)p[SPLAT_LS][e] - LOG_1_6);
   }
-  float child_logit = p[3][0];
+  float child_logit = p[SPLAT_LOGITS][0];
   if (a.revised) {
-    const double o2 = 1.0 - sqrt(1.0 - sigmoid64(p[3][0]));
+    const double o2 = 1.0 - sqrt(1.0 - sigmoid64(p[SPLAT_LOGITS][0]));
     child_logit = (float)log(o2 / (1.0 - o2));
   }
 #pragma unroll
@@ -206,18 +206,18 @@ __global__ void __launch_bounds__(THREADS) densify_rows_kernel(const ApplyP a) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
       const double off = (R[3 * i] * z[0] + R[3 * i + 1] * z[1]) + R[3 * i + 2] * z[2];
-      a.n[0][r[d] * 3 + i] = (float)((double)p[0][i] + off);
-      a.n[1][r[d] * 3 + i] = child_ls[i];
+      a.n[SPLAT_PARAMS][SPLAT_MEANS][r[d] * 3 + i] = (float)((double)p[SPLAT_MEANS][i] + off);
+      a.n[SPLAT_PARAMS][SPLAT_LS][r[d] * 3 + i] = child_ls[i];
     }
 #pragma unroll
-    for (int e = 0; e < 4; ++e) a.n[2][r[d] * 4 + e] = p[2][e];
-    a.n[3][r[d]] = child_logit;
+    for (int e = 0; e < 4; ++e) a.n[SPLAT_PARAMS][SPLAT_QUATS][r[d] * 4 + e] = p[SPLAT_QUATS][e];
+    a.n[SPLAT_PARAMS][SPLAT_LOGITS][r[d]] = child_logit;
 #pragma unroll
-    for (int f = 0; f < 4; ++f)
+    for (int f = 0; f < SPLAT_SH; ++f)
 #pragma unroll
-      for (int e = 0; e < width[f]; ++e) {
-        a.n[5 + f][r[d] * width[f] + e] = 0.f;
-        a.n[10 + f][r[d] * width[f] + e] = 0.f;
+      for (int e = 0, w = splat_width(f, 0); e < w; ++e) {
+        a.n[SPLAT_M][f][r[d] * w + e] = 0.f;
+        a.n[SPLAT_V][f][r[d] * w + e] = 0.f;
       }
   }
 }
@@ -249,9 +249,9 @@ __global__ void __launch_bounds__(THREADS) densify_sh_kernel(const ApplyP a) {
   const long W = 3L * a.K;
   for (int d = 0; d < n; ++d) {
     const bool original = d == 0 && fate != SPLIT;
-    move_row(a.o[4] + g * W, a.n[4] + r[d] * W, (int)W, lane);
-    move_row(original ? a.o[9] + g * W : nullptr, a.n[9] + r[d] * W, (int)W, lane);
-    move_row(original ? a.o[14] + g * W : nullptr, a.n[14] + r[d] * W, (int)W, lane);
+    move_row(a.o[SPLAT_PARAMS][SPLAT_SH] + g * W, a.n[SPLAT_PARAMS][SPLAT_SH] + r[d] * W, (int)W, lane);
+    move_row(original ? a.o[SPLAT_M][SPLAT_SH] + g * W : nullptr, a.n[SPLAT_M][SPLAT_SH] + r[d] * W, (int)W, lane);
+    move_row(original ? a.o[SPLAT_V][SPLAT_SH] + g * W : nullptr, a.n[SPLAT_V][SPLAT_SH] + r[d] * W, (int)W, lane);
   }
 }
 
@@ -314,22 +314,16 @@ extern "C" int v3a_densify_apply(const v3a_densify_apply_args* a, void* stream) 
   if (!a) return V3A_ERR_ARG;
   if (bad_count(a->U) || bad_count(a->U_out) || a->K < 1 || a->K > 1024 || a->U_out > 2 * a->U) return V3A_ERR_SHAPE;
   if (a->U == 0 || a->U_out == 0) return V3A_OK;
-  const float* const o[15] = {a->means, a->log_scales, a->quats, a->logits, a->sh, a->m_means, a->m_log_scales, a->m_quats, a->m_logits, a->m_sh,
-                              a->v_means, a->v_log_scales, a->v_quats, a->v_logits, a->v_sh};
-  float* const n[15] = {a->new_means, a->new_log_scales, a->new_quats, a->new_logits, a->new_sh, a->new_m_means, a->new_m_log_scales,
-                        a->new_m_quats, a->new_m_logits, a->new_m_sh, a->new_v_means, a->new_v_log_scales, a->new_v_quats, a->new_v_logits,
-                        a->new_v_sh};
-  if (!a->fates || !a->offsets || !a->totals) return V3A_ERR_ARG;
-  const long width[5] = {3, 3, 4, 1, 3L * a->K};
-  for (int i = 0; i < 15; ++i)
-    if (!o[i] || !n[i]) return V3A_ERR_ARG;
-  for (int i = 0; i < 15; ++i)
-    for (int j = 0; j < 15; ++j) {
-      if (overlap(n[i], a->U_out * width[i % 5], o[j], a->U * width[j % 5])) return V3A_ERR_SHAPE;
-      if (i != j && overlap(n[i], a->U_out * width[i % 5], n[j], a->U_out * width[j % 5])) return V3A_ERR_SHAPE;
+  ApplyP k = {{SPLAT_SET(a, ), SPLAT_SET(a, m_), SPLAT_SET(a, v_)}, {SPLAT_SET(a, new_), SPLAT_SET(a, new_m_), SPLAT_SET(a, new_v_)}};
+  if (!a->fates || !a->offsets || !a->totals || splat_sets_have_null(k.o) || splat_sets_have_null(k.n)) return V3A_ERR_ARG;
+  for (int i = 0; i < SPLAT_GROUPS * SPLAT_FIELDS; ++i)
+    for (int j = 0; j < SPLAT_GROUPS * SPLAT_FIELDS; ++j) {
+      const int fi = i % SPLAT_FIELDS, fj = j % SPLAT_FIELDS;
+      const long wi = splat_width(fi, 3 * a->K), wj = splat_width(fj, 3 * a->K);
+      const float *ni = k.n[i / SPLAT_FIELDS][fi], *nj = k.n[j / SPLAT_FIELDS][fj], *oj = k.o[j / SPLAT_FIELDS][fj];
+      if (overlap(ni, a->U_out * wi, oj, a->U * wj)) return V3A_ERR_SHAPE;
+      if (i != j && overlap(ni, a->U_out * wi, nj, a->U_out * wj)) return V3A_ERR_SHAPE;
     }
-  ApplyP k;
-  for (int i = 0; i < 15; ++i) { k.o[i] = o[i]; k.n[i] = n[i]; }
   k.fates = a->fates; k.offsets = a->offsets; k.totals = a->totals;
   k.U = a->U; k.U_out = a->U_out; k.K = a->K;
   k.key = make_key(a->seed, 0u, a->step);   // Key.stream is the sampler's; the children name their streams (4-7) at each draw

@@ -15,6 +15,7 @@
 #include "common.h"
 #include "fixed_sum.h"
 #include "splat_quat.h"
+#include "splat_scene.h"
 #include "../../include/vist3a_hip.h"
 
 // Below this line only: quat_R<double> of splat_quat.h is defined above it and may be contracted to FMAs, as it is in post_opt.hip.
@@ -118,8 +119,7 @@ long sample_blocks(long U) { return (U + BLOCK_ELEMS - 1) / BLOCK_ELEMS; }
 
 struct MoveP {
   const int* src; const int* counts;
-  float* p[5]; float* m[5]; float* v[5];   // means, log-scales, quaternions, opacity logits, harmonics
-  int width[5];                            // floats per row: 3, 3, 4, 1, 3 K
+  SplatSet<float> p, m, v; int n_sh;       // n_sh: floats per harmonics row, 3 K
   long U, n_slots, dst_offset;
   double min_opacity;
   float* scratch;                          // [U, 4]: the new (logit, log-scales) of every source
@@ -132,7 +132,7 @@ __global__ void __launch_bounds__(THREADS) mcmc_new_values_kernel(const MoveP a)
   const int cnt = a.counts[j];
   if (cnt < 1) return;
   const int r = cnt + 1 < MAX_RATIO ? cnt + 1 : MAX_RATIO;
-  const double op = sigmoid64(a.p[3][j]);
+  const double op = sigmoid64(a.p[SPLAT_LOGITS][j]);
   const double o1 = 1.0 - pow(1.0 - op, 1.0 / (double)r);
   double den = 0.0;
   for (int i = 1; i <= r; ++i) {
@@ -149,7 +149,13 @@ __global__ void __launch_bounds__(THREADS) mcmc_new_values_kernel(const MoveP a)
   const double o2 = o1 < a.min_opacity ? a.min_opacity : (o1 > hi ? hi : o1);
   a.scratch[j * 4] = (float)log(o2 / (1.0 - o2));
 #pragma unroll
-  for (int e = 0; e < 3; ++e) a.scratch[j * 4 + 1 + e] = (float)log(coef * exp((double)a.p[1][j * 3 + e]));
+  for (int e = 0; e < 3; ++e) a.scratch[j * 4 + 1 + e] = (float)log(coef * exp((double)a.p[SPLAT_LS][j * 3 + e]));
+}
+
+// both moments of row r in all five tensors
+__device__ __forceinline__ void zero_moments(const MoveP& a, long r) {
+  for (int f = 0; f < SPLAT_FIELDS; ++f)
+    for (int e = 0, w = splat_width(f, a.n_sh); e < w; ++e) a.m[f][r * w + e] = a.v[f][r * w + e] = 0.f;
 }
 
 // Threads [0, U): row j as a source takes its new values (and, relocating, loses its moments).  Threads [U, U + n_slots): slot s
@@ -160,15 +166,10 @@ __global__ void __launch_bounds__(THREADS) mcmc_move_kernel(const MoveP a) {
   if (t < a.U) {
     const long j = t;
     if (a.counts[j] < 1) return;
-    a.p[3][j] = a.scratch[j * 4];
+    a.p[SPLAT_LOGITS][j] = a.scratch[j * 4];
 #pragma unroll
-    for (int e = 0; e < 3; ++e) a.p[1][j * 3 + e] = a.scratch[j * 4 + 1 + e];
-    if (!growth)
-      for (int f = 0; f < 5; ++f)
-        for (int e = 0; e < a.width[f]; ++e) {
-          a.m[f][j * a.width[f] + e] = 0.f;
-          a.v[f][j * a.width[f] + e] = 0.f;
-        }
+    for (int e = 0; e < 3; ++e) a.p[SPLAT_LS][j * 3 + e] = a.scratch[j * 4 + 1 + e];
+    if (!growth) zero_moments(a, j);
     return;
   }
   const long s = t - a.U;
@@ -176,20 +177,15 @@ __global__ void __launch_bounds__(THREADS) mcmc_move_kernel(const MoveP a) {
   const long j = a.src[s];
   if (j < 0 || j >= a.U || a.counts[j] < 1) return;
   const long d = a.dst_offset + s;
-  a.p[3][d] = a.scratch[j * 4];
+  a.p[SPLAT_LOGITS][d] = a.scratch[j * 4];
 #pragma unroll
-  for (int e = 0; e < 3; ++e) a.p[1][d * 3 + e] = a.scratch[j * 4 + 1 + e];
+  for (int e = 0; e < 3; ++e) a.p[SPLAT_LS][d * 3 + e] = a.scratch[j * 4 + 1 + e];
 #pragma unroll
-  for (int e = 0; e < 3; ++e) a.p[0][d * 3 + e] = a.p[0][j * 3 + e];
+  for (int e = 0; e < 3; ++e) a.p[SPLAT_MEANS][d * 3 + e] = a.p[SPLAT_MEANS][j * 3 + e];
 #pragma unroll
-  for (int e = 0; e < 4; ++e) a.p[2][d * 4 + e] = a.p[2][j * 4 + e];
-  for (int e = 0; e < a.width[4]; ++e) a.p[4][d * a.width[4] + e] = a.p[4][j * a.width[4] + e];
-  if (growth)
-    for (int f = 0; f < 5; ++f)
-      for (int e = 0; e < a.width[f]; ++e) {
-        a.m[f][d * a.width[f] + e] = 0.f;
-        a.v[f][d * a.width[f] + e] = 0.f;
-      }
+  for (int e = 0; e < 4; ++e) a.p[SPLAT_QUATS][d * 4 + e] = a.p[SPLAT_QUATS][j * 4 + e];
+  for (int e = 0; e < a.n_sh; ++e) a.p[SPLAT_SH][d * a.n_sh + e] = a.p[SPLAT_SH][j * a.n_sh + e];
+  if (growth) zero_moments(a, d);
 }
 
 // ------------------------------------------------------------------------------------------------------------------ noise
@@ -279,11 +275,8 @@ extern "C" long v3a_mcmc_relocate_workspace_bytes(long U) {
 
 extern "C" int v3a_mcmc_relocate(const v3a_mcmc_relocate_args* a, void* stream) {
   if (!a || !a->src || !a->counts) return V3A_ERR_ARG;
-  float* const p[5] = {a->means, a->log_scales, a->quats, a->logits, a->sh};
-  float* const m[5] = {a->m_means, a->m_log_scales, a->m_quats, a->m_logits, a->m_sh};
-  float* const v[5] = {a->v_means, a->v_log_scales, a->v_quats, a->v_logits, a->v_sh};
-  for (int f = 0; f < 5; ++f)
-    if (!p[f] || !m[f] || !v[f]) return V3A_ERR_ARG;
+  const SplatSet<float> g[SPLAT_GROUPS] = {SPLAT_SET(a, ), SPLAT_SET(a, m_), SPLAT_SET(a, v_)};
+  if (splat_sets_have_null(g)) return V3A_ERR_ARG;
   if (a->U < 1 || bad_count(a->U) || a->n_slots < 1 || bad_count(a->n_slots) || a->K < 1 || a->K > 1024) return V3A_ERR_SHAPE;
   if (a->dst_offset == 0 ? a->n_slots != a->U : a->dst_offset != a->U) return V3A_ERR_SHAPE;   // relocation : growth
   if (a->dst_offset + a->n_slots > 0x7fffffffL) return V3A_ERR_SHAPE;
@@ -291,8 +284,7 @@ extern "C" int v3a_mcmc_relocate(const v3a_mcmc_relocate_args* a, void* stream) 
   if (bad_workspace(a->workspace, a->workspace_bytes, v3a_mcmc_relocate_workspace_bytes(a->U))) return V3A_ERR_WORKSPACE;
   MoveP k;
   k.src = a->src; k.counts = a->counts;
-  const int width[5] = {3, 3, 4, 1, 3 * a->K};
-  for (int f = 0; f < 5; ++f) { k.p[f] = p[f]; k.m[f] = m[f]; k.v[f] = v[f]; k.width[f] = width[f]; }
+  k.p = g[SPLAT_PARAMS]; k.m = g[SPLAT_M]; k.v = g[SPLAT_V]; k.n_sh = 3 * a->K;
   k.U = a->U; k.n_slots = a->n_slots; k.dst_offset = a->dst_offset;
   k.min_opacity = a->min_opacity;
   k.scratch = (float*)a->workspace;

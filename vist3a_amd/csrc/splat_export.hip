@@ -17,6 +17,7 @@
 // for the whole file, and the divisions are spelled __fdiv_rn.  expf / sqrtf are the device library's (within 1 ulp).
 #include "common.h"
 #include "int_scan.h"
+#include "splat_scene.h"
 #include "../../include/vist3a_hip.h"
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -27,22 +28,15 @@ namespace {
 constexpr int THREADS = 256;
 constexpr int CHUNK = 256;             // splats per chunk of the compressed PLY = lanes per workgroup
 constexpr int RANGE_BLOCKS = 256;      // at most this many partial ranges: one workgroup of the key kernel reduces them
-constexpr float SH_C0 = 0.28209479177387814f;
 
-struct Scene {
-  const float *means, *ls, *quats, *logits, *sh;
-  long ld_means, ld_ls, ld_quats, ld_logits, ld_sh;
-  long U;
-  int K, xyzw;
-};
+typedef SplatView<const float> Scene;
 
-__device__ __forceinline__ bool finite32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 __device__ __forceinline__ float sigmoid32(float x) { return __fdiv_rn(1.0f, 1.0f + expf(-x)); }
 __device__ __forceinline__ float dc_colour(float sh0) { return sh0 * SH_C0 + 0.5f; }   // sh2rgb: a product, then a sum
 
 // the quaternion of row r in the file's order (w, x, y, z)
 __device__ __forceinline__ void load_quat(const Scene& s, long r, float* q) {
-  const float* p = s.quats + r * s.ld_quats;
+  const float* p = s.quats(r);
   if (s.xyzw) { q[0] = p[3]; q[1] = p[0]; q[2] = p[1]; q[3] = p[2]; }
   else { q[0] = p[0]; q[1] = p[1]; q[2] = p[2]; q[3] = p[3]; }
 }
@@ -67,20 +61,20 @@ __global__ void __launch_bounds__(THREADS) export_flags_kernel(const FilterP a) 
   bad[threadIdx.x] = 0;
   __syncthreads();
   const int W = 3 * (s.K + 1);
-  const long rows_here = s.U - row0 < THREADS ? s.U - row0 : THREADS;
+  const long rows_here = s.rows - row0 < THREADS ? s.rows - row0 : THREADS;
   for (long e = threadIdx.x; e < rows_here * W; e += THREADS) {
     const int r = (int)(e / W), c = (int)(e - (long)r * W);
-    if (!finite32(s.sh[(row0 + r) * s.ld_sh + c])) bad[r] = 1;
+    if (!finite32(s.sh(row0 + r)[c])) bad[r] = 1;
   }
   __syncthreads();
   int keep = 0;
-  if (g < s.U) {
+  if (g < s.rows) {
     bool ok = !bad[threadIdx.x];
 #pragma unroll
-    for (int e = 0; e < 3; ++e) ok = ok && finite32(s.means[g * s.ld_means + e]) && finite32(s.ls[g * s.ld_ls + e]);
+    for (int e = 0; e < 3; ++e) ok = ok && finite32(s.means(g)[e]) && finite32(s.ls(g)[e]);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) ok = ok && finite32(s.quats[g * s.ld_quats + e]);
-    const float logit = s.logits[g * s.ld_logits];
+    for (int e = 0; e < 4; ++e) ok = ok && finite32(s.quats(g)[e]);
+    const float logit = s.logit(g);
     ok = ok && finite32(logit);
     if (a.by_opacity) ok = ok && sigmoid32(logit) > a.threshold;
     keep = ok ? 1 : 0;
@@ -101,7 +95,7 @@ __global__ void __launch_bounds__(THREADS) export_block_prefix_kernel(const Filt
 __global__ void __launch_bounds__(THREADS) export_scatter_kernel(const FilterP a) {
   __shared__ int buf[THREADS];
   const long g = (long)blockIdx.x * THREADS + threadIdx.x;
-  const int keep = g < a.s.U ? a.flag[g] : 0;
+  const int keep = g < a.s.rows ? a.flag[g] : 0;
   int total;
   const int ex = block_exclusive_scan<THREADS>(keep, buf, total);
   if (keep) a.rows[a.block_tot[blockIdx.x] + ex] = (int)g;
@@ -135,7 +129,7 @@ __global__ void __launch_bounds__(THREADS) export_range_kernel(const SortP a) {
   const float inf = __uint_as_float(0x7f800000u);
   float lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
   for (long i = (long)blockIdx.x * THREADS + threadIdx.x; i < a.n; i += (long)gridDim.x * THREADS) {
-    const float* m = a.s.means + (long)a.rows[i] * a.s.ld_means;
+    const float* m = a.s.means(a.rows[i]);
 #pragma unroll
     for (int e = 0; e < 3; ++e) { lo[e] = fminf(lo[e], m[e]); hi[e] = fmaxf(hi[e], m[e]); }
   }
@@ -172,7 +166,7 @@ __global__ void __launch_bounds__(THREADS) export_keys_kernel(const SortP a) {
   }
   const long i = (long)blockIdx.x * THREADS + threadIdx.x;
   if (i >= a.n) return;
-  const float* m = a.s.means + (long)a.rows[i] * a.s.ld_means;
+  const float* m = a.s.means(a.rows[i]);
   unsigned int q[3];
 #pragma unroll
   for (int e = 0; e < 3; ++e) q[e] = (unsigned int)(int)floorf(__fdiv_rn(m[e] - mn[e], len[e]) * 1024.f);
@@ -227,9 +221,9 @@ __global__ void __launch_bounds__(THREADS) export_compressed_kernel(const PackP 
   float v[9];
 #pragma unroll
   for (int e = 0; e < 3; ++e) {
-    v[e] = s.means[r * s.ld_means + e];
-    v[3 + e] = s.ls[r * s.ld_ls + e];
-    v[6 + e] = dc_colour(s.sh[r * s.ld_sh + (long)e * (s.K + 1)]);
+    v[e] = s.means(r)[e];
+    v[3 + e] = s.ls(r)[e];
+    v[6 + e] = dc_colour(s.sh(r)[(long)e * (s.K + 1)]);
   }
   float lo[9], hi[9];
 #pragma unroll
@@ -280,7 +274,7 @@ __global__ void __launch_bounds__(THREADS) export_compressed_kernel(const PackP 
       rot |= unorm((q[e] * sgn) * 0.70710678118654752f + 0.5f, 1023.f) << (20 - 10 * slot);
       ++slot;
     }
-    const float op = sigmoid32(s.logits[r * s.ld_logits]);
+    const float op = sigmoid32(s.logit(r));
     u32x4 o;
     o[0] = pack_111011(nrm[0], nrm[1], nrm[2]);
     o[1] = rot;
@@ -300,7 +294,7 @@ __global__ void __launch_bounds__(THREADS) export_compressed_kernel(const PackP 
     const int cnt = (int)(nbytes - b0 < 4 ? nbytes - b0 : 4);
     for (int k4 = 0; k4 < cnt; ++k4) {
       const int c = j / K, k = j - c * K;
-      const float x = s.sh[(long)ord[sp] * s.ld_sh + (long)c * (K + 1) + 1 + k];
+      const float x = s.sh(ord[sp])[(long)c * (K + 1) + 1 + k];
       word |= byte_trunc(truncf((x * 0.125f + 0.5f) * 256.f)) << (8 * k4);     // x * 0.125 == x / 8 bit for bit
       if (++j == W3) { j = 0; ++sp; }
     }
@@ -321,14 +315,14 @@ __global__ void __launch_bounds__(THREADS) export_splat_kernel(const PackP a) {
 #pragma unroll
   for (int e = 0; e < 4; ++e) rot |= byte_trunc(__fdiv_rn(q[e], qn) * 128.f + 128.f) << (8 * e);
 #pragma unroll
-  for (int e = 0; e < 3; ++e) col |= byte_trunc(dc_colour(s.sh[r * s.ld_sh + (long)e * (s.K + 1)]) * 255.f) << (8 * e);
-  col |= byte_trunc(sigmoid32(s.logits[r * s.ld_logits]) * 255.f) << 24;
+  for (int e = 0; e < 3; ++e) col |= byte_trunc(dc_colour(s.sh(r)[(long)e * (s.K + 1)]) * 255.f) << (8 * e);
+  col |= byte_trunc(sigmoid32(s.logit(r)) * 255.f) << 24;
   u32x4 o0, o1;
 #pragma unroll
-  for (int e = 0; e < 3; ++e) o0[e] = __float_as_uint(s.means[r * s.ld_means + e]);
-  o0[3] = __float_as_uint(expf(s.ls[r * s.ld_ls]));
-  o1[0] = __float_as_uint(expf(s.ls[r * s.ld_ls + 1]));
-  o1[1] = __float_as_uint(expf(s.ls[r * s.ld_ls + 2]));
+  for (int e = 0; e < 3; ++e) o0[e] = __float_as_uint(s.means(r)[e]);
+  o0[3] = __float_as_uint(expf(s.ls(r)[0]));
+  o1[0] = __float_as_uint(expf(s.ls(r)[1]));
+  o1[1] = __float_as_uint(expf(s.ls(r)[2]));
   o1[2] = col;
   o1[3] = rot;
   a.splat[2 * i] = o0;
@@ -345,26 +339,20 @@ __global__ void __launch_bounds__(THREADS) export_ply_kernel(const PackP a) {
   const int c = (int)(e - i * Wo);
   const long r = a.order[i];
   float v;
-  if (c < 3) v = s.means[r * s.ld_means + c];
-  else if (c < 6) v = s.sh[r * s.ld_sh + (long)(c - 3) * (K + 1)];
-  else if (c < 6 + 3 * K) { const int j = c - 6, ch = j / K; v = s.sh[r * s.ld_sh + (long)ch * (K + 1) + 1 + (j - ch * K)]; }
-  else if (c == 6 + 3 * K) v = s.logits[r * s.ld_logits];
-  else if (c < 10 + 3 * K) v = s.ls[r * s.ld_ls + (c - 7 - 3 * K)];
-  else { const int w = c - 10 - 3 * K; v = s.quats[r * s.ld_quats + (s.xyzw ? (w + 3) & 3 : w)]; }
+  if (c < 3) v = s.means(r)[c];
+  else if (c < 6) v = s.sh(r)[(long)(c - 3) * (K + 1)];
+  else if (c < 6 + 3 * K) { const int j = c - 6, ch = j / K; v = s.sh(r)[(long)ch * (K + 1) + 1 + (j - ch * K)]; }
+  else if (c == 6 + 3 * K) v = s.logit(r);
+  else if (c < 10 + 3 * K) v = s.ls(r)[c - 7 - 3 * K];
+  else { const int w = c - 10 - 3 * K; v = s.quats(r)[s.quat_slot(w)]; }
   a.ply[e] = v;
 }
 
 // the scene part of the arguments: V3A_OK, or the error code
 int scene_of(const v3a_splat_export_args* a, Scene& s) {
   if (!a) return V3A_ERR_ARG;
-  if (bad_count(a->U) || a->K < 0 || a->K > 1024) return V3A_ERR_SHAPE;
-  if (a->U == 0) return V3A_OK;
-  if (!a->means || !a->log_scales || !a->quats || !a->logits || !a->sh) return V3A_ERR_ARG;
-  if (a->ld_means < 3 || a->ld_log_scales < 3 || a->ld_quats < 4 || a->ld_logits < 1 || a->ld_sh < 3L * (a->K + 1)) return V3A_ERR_SHAPE;
-  s.means = a->means; s.ls = a->log_scales; s.quats = a->quats; s.logits = a->logits; s.sh = a->sh;
-  s.ld_means = a->ld_means; s.ld_ls = a->ld_log_scales; s.ld_quats = a->ld_quats; s.ld_logits = a->ld_logits; s.ld_sh = a->ld_sh;
-  s.U = a->U; s.K = a->K; s.xyzw = a->quats_xyzw != 0;
-  return V3A_OK;
+  if (a->K > 1024) return V3A_ERR_SHAPE;
+  return splat_view_of(a, a->U, a->K, s);
 }
 
 // the survivor list of a sort / pack call
@@ -382,16 +370,14 @@ extern "C" long v3a_splat_export_filter_workspace_bytes(long U, int K) {
 }
 
 extern "C" int v3a_splat_export_filter(const v3a_splat_export_args* a, void* stream_) {
-  Scene s{};
-  const int rc = scene_of(a, s);
+  FilterP k{};
+  const int rc = scene_of(a, k.s);
   if (rc != V3A_OK) return rc;
   if (!a->count) return V3A_ERR_ARG;
   hipStream_t stream = (hipStream_t)stream_;
   if (a->U == 0) return hipMemsetAsync(a->count, 0, sizeof(long), stream) == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
   if (!a->rows) return V3A_ERR_ARG;
   if (bad_workspace(a->workspace, a->workspace_bytes, v3a_splat_export_filter_workspace_bytes(a->U, a->K))) return V3A_ERR_WORKSPACE;
-  FilterP k;
-  k.s = s;
   k.by_opacity = a->filter_opacity != 0; k.threshold = a->opacity_threshold;
   k.flag = (unsigned char*)a->workspace;
   k.block_tot = (int*)((char*)a->workspace + align256((size_t)a->U));
@@ -411,8 +397,8 @@ extern "C" long v3a_splat_export_sort_workspace_bytes(long U, int K) {
 }
 
 extern "C" int v3a_splat_export_sort(const v3a_splat_export_args* a, void* stream_) {
-  Scene s{};
-  int rc = scene_of(a, s);
+  SortP k{};
+  int rc = scene_of(a, k.s);
   if (rc != V3A_OK) return rc;
   if ((rc = list_of(a, a->rows)) != V3A_OK) return rc;
   if (a->n == 0) return V3A_OK;
@@ -421,8 +407,6 @@ extern "C" int v3a_splat_export_sort(const v3a_splat_export_args* a, void* strea
   if (bad_workspace(a->workspace, a->workspace_bytes, (long)l.total)) return V3A_ERR_WORKSPACE;
   hipStream_t stream = (hipStream_t)stream_;
   char* ws = (char*)a->workspace;
-  SortP k;
-  k.s = s;
   k.rows = a->rows; k.n = a->n;
   k.part = (float*)(ws + l.part);
   const long nb = blocks_for(a->n, THREADS);
@@ -442,46 +426,43 @@ extern "C" int v3a_splat_export_sort(const v3a_splat_export_args* a, void* strea
 }
 
 extern "C" int v3a_splat_export_pack_compressed(const v3a_splat_export_args* a, void* stream) {
-  Scene s{};
-  int rc = scene_of(a, s);
+  PackP k{};
+  int rc = scene_of(a, k.s);
   if (rc != V3A_OK) return rc;
   if ((rc = list_of(a, a->order)) != V3A_OK) return rc;
   if (a->n == 0) return V3A_OK;
   if (!a->out_chunks || !a->out_vertices || (a->K > 0 && !a->out_sh)) return V3A_ERR_ARG;
   if (((uintptr_t)a->out_chunks & 3) || ((uintptr_t)a->out_vertices & 15) || ((uintptr_t)a->out_sh & 3)) return V3A_ERR_SHAPE;
-  PackP k{};
-  k.s = s; k.order = a->order; k.n = a->n;
+  k.order = a->order; k.n = a->n;
   k.chunks = a->out_chunks; k.vertices = (u32x4*)a->out_vertices; k.shbytes = a->out_sh;
   hipLaunchKernelGGL(export_compressed_kernel, dim3(blocks_for(a->n, CHUNK)), dim3(THREADS), 0, (hipStream_t)stream, k);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
 extern "C" int v3a_splat_export_pack_splat(const v3a_splat_export_args* a, void* stream) {
-  Scene s{};
-  int rc = scene_of(a, s);
+  PackP k{};
+  int rc = scene_of(a, k.s);
   if (rc != V3A_OK) return rc;
   if ((rc = list_of(a, a->order)) != V3A_OK) return rc;
   if (a->n == 0) return V3A_OK;
   if (!a->out_splat) return V3A_ERR_ARG;
   if ((uintptr_t)a->out_splat & 15) return V3A_ERR_SHAPE;
-  PackP k{};
-  k.s = s; k.order = a->order; k.n = a->n;
+  k.order = a->order; k.n = a->n;
   k.splat = (u32x4*)a->out_splat;
   hipLaunchKernelGGL(export_splat_kernel, dim3(blocks_for(a->n, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, k);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }
 
 extern "C" int v3a_splat_export_pack_ply(const v3a_splat_export_args* a, void* stream) {
-  Scene s{};
-  int rc = scene_of(a, s);
+  PackP k{};
+  int rc = scene_of(a, k.s);
   if (rc != V3A_OK) return rc;
   if ((rc = list_of(a, a->rows)) != V3A_OK) return rc;
   if (a->n == 0) return V3A_OK;
   if (!a->out_ply) return V3A_ERR_ARG;
   const long total = a->n * (14 + 3L * a->K);
   if (((uintptr_t)a->out_ply & 3) || blocks_for(total, THREADS) > 0x7fffffffL) return V3A_ERR_SHAPE;
-  PackP k{};
-  k.s = s; k.order = a->rows; k.n = a->n;
+  k.order = a->rows; k.n = a->n;
   k.ply = a->out_ply;
   hipLaunchKernelGGL(export_ply_kernel, dim3(blocks_for(total, THREADS)), dim3(THREADS), 0, (hipStream_t)stream, k);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;

@@ -20,6 +20,7 @@
 #include "common.h"
 #include "fixed_sum.h"
 #include "int_scan.h"
+#include "splat_scene.h"
 #include "../../include/vist3a_hip.h"
 
 #pragma clang fp contract(off)
@@ -30,19 +31,10 @@ constexpr int THREADS = 256;
 constexpr int CHUNK = 256;             // splats per chunk of the compressed PLY = lanes per workgroup
 constexpr int MAX_P = 4096;            // floats per row of a float PLY: the column table is LDS
 constexpr int MAX_K = 63;
-constexpr float SH_C0 = 0.28209479177387814f;
 constexpr float SQRT2 = 1.4142135623730951f;
 
-struct Out {
-  float *means, *ls, *quats, *logits, *sh;
-  long ld_means, ld_ls, ld_quats, ld_logits, ld_sh;
-  long n;
-  int K, xyzw;
-};
+typedef SplatView<float> Out;
 
-__device__ __forceinline__ bool finite32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-// where component e of a quaternion in the files' order (w x y z) is stored
-__device__ __forceinline__ int quat_slot(const Out& o, int e) { return o.xyzw ? (e + 3) & 3 : e; }
 // the logit of an opacity code c in (0, 255): exact operands, one division, one logf
 __device__ __forceinline__ float logit_of_code(float c) { return logf(__fdiv_rn(c, 255.f - c)); }
 __device__ __forceinline__ float unlerp(float lo, float hi, unsigned int code, float top) { return lo + (hi - lo) * __fdiv_rn((float)code, top); }
@@ -61,8 +53,6 @@ __global__ void __launch_bounds__(THREADS) import_bad_total_kernel(int* block_to
 }
 
 // --------------------------------------------------------------------------------------------------------------- float PLY
-
-enum { TO_MEANS = 0, TO_LS = 1, TO_QUATS = 2, TO_LOGITS = 3, TO_SH = 4 };
 
 struct PlyP {
   Out o;
@@ -86,20 +76,20 @@ __global__ void __launch_bounds__(THREADS) import_ply_kernel(const PlyP a) {
 #pragma unroll
     for (int k = 1; k < 15; ++k) if (t == k) col = a.off[k];
     int code;
-    if (t < 3) code = (TO_MEANS << 16) | t;
-    else if (t < 6) code = (TO_SH << 16) | ((t - 3) * (K + 1));
-    else if (t == 7) code = TO_LOGITS << 16;
-    else if (t < 11) code = (TO_LS << 16) | (t - 8);
-    else code = (TO_QUATS << 16) | quat_slot(o, t - 11);
+    if (t < 3) code = (SPLAT_MEANS << 16) | t;
+    else if (t < 6) code = (SPLAT_SH << 16) | ((t - 3) * (K + 1));
+    else if (t == 7) code = SPLAT_LOGITS << 16;
+    else if (t < 11) code = (SPLAT_LS << 16) | (t - 8);
+    else code = (SPLAT_QUATS << 16) | o.quat_slot(t - 11);
     lut[col] = code;
   }
   for (int j = t; j < a.n_rest; j += THREADS) {
     const int c = j / K, k = j - c * K;
-    lut[a.off[6] + j] = (TO_SH << 16) | (c * (K + 1) + 1 + k);
+    lut[a.off[6] + j] = (SPLAT_SH << 16) | (c * (K + 1) + 1 + k);
   }
   __syncthreads();
   const long row0 = (long)blockIdx.x * THREADS;
-  const int rows_here = (int)(o.n - row0 < THREADS ? o.n - row0 : THREADS);
+  const int rows_here = (int)(o.rows - row0 < THREADS ? o.rows - row0 : THREADS);
   const int total = rows_here * P;                       // <= 256 * 4096
   const float* src = a.in + row0 * P;
   const int dq = THREADS / P, dr = THREADS - dq * P;     // a lane's step of 256 floats = dq rows and dr columns
@@ -110,12 +100,13 @@ __global__ void __launch_bounds__(THREADS) import_ply_kernel(const PlyP a) {
     if (code >= 0) {
       float v = src[e];
       const int kind = code >> 16, idx = code & 0xffff;
-      if (kind == TO_LOGITS && a.linear) {
+      if (kind == SPLAT_LOGITS && a.linear) {
         v = v < 1e-6f ? 1e-6f : (v > hi ? hi : v);       // a NaN stays a NaN
         v = logf(__fdiv_rn(v, 1.f - v));
       }
-      float* base = kind == TO_MEANS ? o.means : kind == TO_LS ? o.ls : kind == TO_QUATS ? o.quats : kind == TO_LOGITS ? o.logits : o.sh;
-      const long ld = kind == TO_MEANS ? o.ld_means : kind == TO_LS ? o.ld_ls : kind == TO_QUATS ? o.ld_quats : kind == TO_LOGITS ? o.ld_logits : o.ld_sh;
+      // o.p[kind] spelled as selects: the view stays in scalar registers
+      float* base = kind == SPLAT_MEANS ? o.p[SPLAT_MEANS] : kind == SPLAT_LS ? o.p[SPLAT_LS] : kind == SPLAT_QUATS ? o.p[SPLAT_QUATS] : kind == SPLAT_LOGITS ? o.p[SPLAT_LOGITS] : o.p[SPLAT_SH];
+      const long ld = kind == SPLAT_MEANS ? o.ld[SPLAT_MEANS] : kind == SPLAT_LS ? o.ld[SPLAT_LS] : kind == SPLAT_QUATS ? o.ld[SPLAT_QUATS] : kind == SPLAT_LOGITS ? o.ld[SPLAT_LOGITS] : o.ld[SPLAT_SH];
       base[(row0 + r) * ld + idx] = v;
       if (!finite32(v)) bad[r] = 1;                      // every writer stores the same 1
     }
@@ -142,7 +133,7 @@ __global__ void __launch_bounds__(THREADS) import_compressed_kernel(const CompP 
   const Out& o = a.o;
   const int t = threadIdx.x, K = o.K, W3 = 3 * K;
   const long first = (long)blockIdx.x * CHUNK, i = first + t;
-  const int m = (int)(o.n - first < CHUNK ? o.n - first : CHUNK);     // splats of this chunk
+  const int m = (int)(o.rows - first < CHUNK ? o.rows - first : CHUNK);     // splats of this chunk
   if (t < 18) bnd[t] = a.chunks[(long)blockIdx.x * 18 + t];
   if (t < W3) { const int c = t / K; col[t] = c * (K + 1) + 1 + (t - c * K); }
   __syncthreads();
@@ -159,14 +150,14 @@ __global__ void __launch_bounds__(THREADS) import_compressed_kernel(const CompP 
       const float mean = unlerp(bnd[e], bnd[3 + e], pc[e], top[e]);
       const float ls = unlerp(bnd[6 + e], bnd[9 + e], sc[e], top[e]);
       const float sh0 = __fdiv_rn(unlerp(bnd[12 + e], bnd[15 + e], cc[e], 255.f) - 0.5f, SH_C0);
-      o.means[i * o.ld_means + e] = mean;
-      o.ls[i * o.ld_ls + e] = ls;
-      o.sh[i * o.ld_sh + (long)e * (K + 1)] = sh0;
+      o.means(i)[e] = mean;
+      o.ls(i)[e] = ls;
+      o.sh(i)[(long)e * (K + 1)] = sh0;
       ok = ok && finite32(mean) && finite32(ls) && finite32(sh0);
     }
     flag = ok ? 0 : 1;                                   // the logit and the quaternion of a code are always finite
     const float c = fminf(fmaxf((float)(rgba & 255u), 0.5f), 254.5f);
-    o.logits[i * o.ld_logits] = logit_of_code(c);
+    o.logit(i) = logit_of_code(c);
     float v[3];
 #pragma unroll
     for (int e = 0; e < 3; ++e) v[e] = (__fdiv_rn((float)((rot >> (20 - 10 * e)) & 1023u), 1023.f) - 0.5f) * SQRT2;
@@ -176,7 +167,7 @@ __global__ void __launch_bounds__(THREADS) import_compressed_kernel(const CompP 
     for (int e = 0; e < 4; ++e) {                        // the stored three fill the other places in ascending order
       const int slot = e - (e > big ? 1 : 0);
       const float q = e == big ? dropped : (slot == 0 ? v[0] : slot == 1 ? v[1] : v[2]);
-      o.quats[i * o.ld_quats + quat_slot(o, e)] = q;
+      o.quats(i)[o.quat_slot(e)] = q;
     }
   }
   // the chunk's harmonics bytes: byte b of the chunk is coefficient j = b % 3K of its splat b / 3K; a lane's step of 256 bytes is
@@ -188,7 +179,7 @@ __global__ void __launch_bounds__(THREADS) import_compressed_kernel(const CompP 
     int sp = t / W3, j = t - sp * W3;
     for (int e = t; e < nbytes; e += THREADS) {
       const float x = (((float)src[e] + 0.5f) * 0.00390625f - 0.5f) * 8.f;     // * 2^-8 == / 256 bit for bit
-      o.sh[(first + sp) * o.ld_sh + col[j]] = x;
+      o.sh(first + sp)[col[j]] = x;
       j += dr;
       sp += dq;
       if (j >= W3) { j -= W3; ++sp; }
@@ -210,7 +201,7 @@ __global__ void __launch_bounds__(THREADS) import_splat_kernel(const SplatP a) {
   const Out& o = a.o;
   const long i = (long)blockIdx.x * THREADS + threadIdx.x;
   int flag = 0;
-  if (i < o.n) {
+  if (i < o.rows) {
     unsigned int w[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) w[e] = a.in[8 * i + e];
@@ -220,37 +211,30 @@ __global__ void __launch_bounds__(THREADS) import_splat_kernel(const SplatP a) {
       const float mean = __uint_as_float(w[e]);
       const float ls = logf(__uint_as_float(w[3 + e]));   // a scale <= 0, NaN or Inf leaves a non-finite log: the row is bad
       const float rgb = __fdiv_rn((float)((w[6] >> (8 * e)) & 255u) + 0.5f, 255.f);
-      o.means[i * o.ld_means + e] = mean;
-      o.ls[i * o.ld_ls + e] = ls;
-      o.sh[i * o.ld_sh + e] = __fdiv_rn(rgb - 0.5f, SH_C0);
+      o.means(i)[e] = mean;
+      o.ls(i)[e] = ls;
+      o.sh(i)[e] = __fdiv_rn(rgb - 0.5f, SH_C0);
       ok = ok && finite32(mean) && finite32(ls);
     }
     flag = ok ? 0 : 1;
-    o.logits[i * o.ld_logits] = logit_of_code(fminf(fmaxf((float)(w[6] >> 24) + 0.5f, 0.5f), 254.5f));
+    o.logit(i) = logit_of_code(fminf(fmaxf((float)(w[6] >> 24) + 0.5f, 0.5f), 254.5f));
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      o.quats[i * o.ld_quats + quat_slot(o, e)] = ((float)((w[7] >> (8 * e)) & 255u) + 0.5f - 128.f) * 0.0078125f;   // / 128, exact
+      o.quats(i)[o.quat_slot(e)] = ((float)((w[7] >> (8 * e)) & 255u) + 0.5f - 128.f) * 0.0078125f;   // / 128, exact
   }
   store_block_total(flag, red, a.block_tot);
 }
 
 // --------------------------------------------------------------------------------------------------------------- host side
 
-// the output part of the arguments: V3A_OK with `go` set when there is something to launch, or the error code
-int out_of(const v3a_splat_import_args* a, Out& o, bool& go) {
-  go = false;
+// the output part of the arguments: V3A_OK, with o.rows > 0 when there is something to launch, or the error code
+int out_of(const v3a_splat_import_args* a, Out& o) {
   if (!a) return V3A_ERR_ARG;
   if (bad_count(a->n) || a->n_rest < 0 || a->n_rest % 3 != 0 || a->n_rest / 3 > MAX_K) return V3A_ERR_SHAPE;
-  if (a->n == 0) return V3A_OK;
-  if (!a->means || !a->log_scales || !a->quats || !a->logits || !a->sh || !a->bad || !a->payload) return V3A_ERR_ARG;
-  const int K = a->n_rest / 3;
-  if (a->ld_means < 3 || a->ld_log_scales < 3 || a->ld_quats < 4 || a->ld_logits < 1 || a->ld_sh < 3L * (K + 1)) return V3A_ERR_SHAPE;
-  if ((uintptr_t)a->payload & 3) return V3A_ERR_SHAPE;
-  o.means = a->means; o.ls = a->log_scales; o.quats = a->quats; o.logits = a->logits; o.sh = a->sh;
-  o.ld_means = a->ld_means; o.ld_ls = a->ld_log_scales; o.ld_quats = a->ld_quats; o.ld_logits = a->ld_logits; o.ld_sh = a->ld_sh;
-  o.n = a->n; o.K = K; o.xyzw = a->quats_xyzw != 0;
-  go = true;
-  return V3A_OK;
+  if (a->n > 0 && (!a->bad || !a->payload)) return V3A_ERR_ARG;
+  const int rc = splat_view_of(a, a->n, a->n_rest / 3, o);
+  if (rc == V3A_OK && a->n > 0 && ((uintptr_t)a->payload & 3)) return V3A_ERR_SHAPE;
+  return rc;
 }
 
 int workspace_of(const v3a_splat_import_args* a) {
@@ -272,9 +256,8 @@ extern "C" long v3a_splat_import_workspace_bytes(long n) {
 
 extern "C" int v3a_splat_import_ply(const v3a_splat_import_args* a, void* stream_) {
   PlyP k{};
-  bool go;
-  int rc = out_of(a, k.o, go);
-  if (rc != V3A_OK || !go) return rc;
+  int rc = out_of(a, k.o);
+  if (rc != V3A_OK || k.o.rows == 0) return rc;
   const int P = a->P;
   if (P < 14 + a->n_rest || P > MAX_P) return V3A_ERR_SHAPE;
   for (int e = 0; e < 15; ++e) {
@@ -298,9 +281,8 @@ extern "C" int v3a_splat_import_ply(const v3a_splat_import_args* a, void* stream
 
 extern "C" int v3a_splat_import_compressed(const v3a_splat_import_args* a, void* stream_) {
   CompP k{};
-  bool go;
-  int rc = out_of(a, k.o, go);
-  if (rc != V3A_OK || !go) return rc;
+  int rc = out_of(a, k.o);
+  if (rc != V3A_OK || k.o.rows == 0) return rc;
   if (a->nch != blocks_for(a->n, CHUNK) || a->payload_bytes != 72L * a->nch + 16L * a->n + (long)a->n_rest * a->n) return V3A_ERR_SHAPE;
   if ((rc = workspace_of(a)) != V3A_OK) return rc;
   k.chunks = (const float*)a->payload;
@@ -314,9 +296,8 @@ extern "C" int v3a_splat_import_compressed(const v3a_splat_import_args* a, void*
 
 extern "C" int v3a_splat_import_splat(const v3a_splat_import_args* a, void* stream_) {
   SplatP k{};
-  bool go;
-  int rc = out_of(a, k.o, go);
-  if (rc != V3A_OK || !go) return rc;
+  int rc = out_of(a, k.o);
+  if (rc != V3A_OK || k.o.rows == 0) return rc;
   if (a->n_rest != 0 || a->payload_bytes != 32L * a->n) return V3A_ERR_SHAPE;
   if ((rc = workspace_of(a)) != V3A_OK) return rc;
   k.in = (const unsigned int*)a->payload;

@@ -5,6 +5,7 @@ libvist3a_hip.so.  Every wrapper validates dtype/device/contiguity and raises on
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import threading
 from typing import Optional
@@ -1887,17 +1888,36 @@ def mcmc_sample(weights: torch.Tensor, *, min_weight: float, alive_only: bool, n
 SPLAT_TENSORS = ("means", "scales", "quats", "opacities", "sh")   # a scene's five tensors, in the order of lib.SPLAT_FIELDS
 
 
+def _splat_inner(K: int) -> dict:   # the shape of one row of each tensor; K = the last dimension of sh (the DC term included where stored)
+    return dict(means=(3,), scales=(3,), quats=(4,), opacities=(), sh=(3, K))
+
+
 def _splat_dicts(what: str, params: dict, m: dict, v: dict, rows: int) -> int:
     """`params`, `m` and `v` each hold the five SPLAT_TENSORS as contiguous f32 device tensors of `rows` rows -> K of sh [rows,3,K]"""
     sh = params["sh"]
     if sh.dim() != 3 or sh.shape[1] != 3 or sh.shape[2] < 1:
         raise ValueError(f"{what}: sh must be [rows,3,K], got {tuple(sh.shape)}")
     K = sh.shape[2]
-    shapes = dict(means=(rows, 3), scales=(rows, 3), quats=(rows, 4), opacities=(rows,), sh=(rows, 3, K))
     for group, d in (("params", params), ("m", m), ("v", v)):
-        for name in SPLAT_TENSORS:
-            _f32_dev(d[name], f"{group}[{name!r}]", shapes[name])
+        for name, inner in _splat_inner(K).items():
+            _f32_dev(d[name], f"{group}[{name!r}]", (rows,) + inner)
     return K
+
+
+def _scene_view(args, tensors: dict, rows: int, K_plus: int, what: str, label: str) -> None:
+    """Sets the five pointers and row strides (`field`, `ld_field`) of a SplatExportArgs / SplatImportArgs from `tensors`: float32 device
+    tensors [rows, ...], sh [rows,3,K_plus], whose rows may be strided (a row's own elements contiguous).  `label` formats a name."""
+    for field, (name, inner) in zip(L.SPLAT_FIELDS, _splat_inner(K_plus).items()):
+        t, shape, width = tensors[name], (rows,) + inner, math.prod(inner)
+        if not t.is_cuda or t.dtype != f32 or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: {label.format(name)} must be a float32 device tensor (the HIP path has no CPU fallback) of shape {shape}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        if rows > 0 and width > 1 and not t[0].is_contiguous():
+            raise ValueError(f"{what}: the elements of a row of {label.format(name)} must be contiguous, got strides {t.stride()}")
+        ld = t.stride(0) if rows > 1 else width
+        if ld < width:
+            raise ValueError(f"{what}: rows of {label.format(name)} overlap (row stride {ld} < {width})")
+        setattr(args, field, t.data_ptr())
+        setattr(args, "ld_" + field, ld)
 
 
 def mcmc_relocate(src: torch.Tensor, counts: torch.Tensor, params: dict, m: dict, v: dict, *, dst_offset: int, min_opacity: float) -> None:
@@ -2050,24 +2070,8 @@ def _export_scene(scene: dict, quats_xyzw: bool, what: str) -> L.SplatExportArgs
     if means.dim() != 2 or means.shape[1] != 3 or sh.dim() != 3 or sh.shape[1] != 3 or sh.shape[2] < 1:
         raise ValueError(f"{what}: means [U,3] and sh [U,3,K+1] required, got {tuple(means.shape)} and {tuple(sh.shape)}")
     U, K = means.shape[0], sh.shape[2] - 1
-    inner = dict(means=(3,), scales=(3,), quats=(4,), opacities=(), sh=(3, K + 1))
     a = L.SplatExportArgs()
-    for field, name in zip(L.SPLAT_FIELDS, SPLAT_TENSORS):
-        t = scene[name]
-        if not t.is_cuda or t.dtype != f32:
-            raise ValueError(f"{what}: {name} must be a float32 device tensor (the HIP path has no CPU fallback), got {t.dtype} on {t.device}")
-        if tuple(t.shape) != (U,) + inner[name]:
-            raise ValueError(f"{what}: {name} must have shape {(U,) + inner[name]}, got {tuple(t.shape)}")
-        width = 1
-        for n in inner[name]:
-            width *= n
-        if U > 0 and width > 1 and not t[0].is_contiguous():
-            raise ValueError(f"{what}: the elements of a row of {name} must be contiguous, got strides {t.stride()}")
-        ld = t.stride(0) if U > 1 else width
-        if ld < width:
-            raise ValueError(f"{what}: rows of {name} overlap (row stride {ld} < {width})")
-        setattr(a, field, t.data_ptr())
-        setattr(a, "ld_" + field, ld)
+    _scene_view(a, scene, U, K + 1, what, "{}")
     a.U, a.K, a.quats_xyzw = U, K, int(bool(quats_xyzw))
     return a
 
@@ -2153,24 +2157,10 @@ PLY_COLUMNS = (("x", "y", "z") + tuple(f"f_dc_{j}" for j in range(3)) + ("f_rest
 def _import_outputs(n: int, K: int, dev, out: Optional[dict], what: str):
     """The five output tensors of a load - fresh, or the caller's (strided rows allowed, as for the exporter) - and the args struct
     with them, `bad` and the workspace set.  -> (args, scene dict, bad int32 [1], workspace)"""
-    inner = dict(means=(3,), scales=(3,), quats=(4,), opacities=(), sh=(3, K + 1))
     if out is None:
-        out = {name: torch.empty((n,) + inner[name], device=dev, dtype=f32) for name in SPLAT_TENSORS}
+        out = {name: torch.empty((n,) + inner, device=dev, dtype=f32) for name, inner in _splat_inner(K + 1).items()}
     a = L.SplatImportArgs()
-    for field, name in zip(L.SPLAT_FIELDS, SPLAT_TENSORS):
-        t = out[name]
-        if not t.is_cuda or t.dtype != f32 or tuple(t.shape) != (n,) + inner[name]:
-            raise ValueError(f"{what}: out[{name!r}] must be a float32 device tensor of shape {(n,) + inner[name]}, got {t.dtype} {tuple(t.shape)} on {t.device}")
-        width = 1
-        for w in inner[name]:
-            width *= w
-        if n > 0 and width > 1 and not t[0].is_contiguous():
-            raise ValueError(f"{what}: the elements of a row of out[{name!r}] must be contiguous, got strides {t.stride()}")
-        ld = t.stride(0) if n > 1 else width
-        if ld < width:
-            raise ValueError(f"{what}: rows of out[{name!r}] overlap (row stride {ld} < {width})")
-        setattr(a, field, t.data_ptr())
-        setattr(a, "ld_" + field, ld)
+    _scene_view(a, out, n, K + 1, what, "out[{!r}]")
     bad = torch.zeros(1, device=dev, dtype=torch.int32)
     ws = None
     if n > 0:
