@@ -38,7 +38,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 34) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 36) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -800,6 +800,30 @@ typedef struct {
   double beta1, beta2, eps, bias_correction1, bias_correction2;
 } v3a_adam_args;
 int v3a_adam_step(const v3a_adam_args* a, void* stream);
+
+/* The step's visibility mask (csrc/post_opt.hip; simple_trainer.py:1111, (info["radii"] > 0).any(0)): radii int32 [C,U] as
+ * v3a_gs_project writes them -> visible uint8 [U], 1 where radii[c,g] > 0 for some camera c, else 0.  One thread per Gaussian,
+ * the cameras walked in index order; every output byte is written exactly once (no atomics, no memset).  C >= 1, U >= 1. */
+int v3a_gs_visibility(const int* radii, int C, long U, uint8_t* visible, void* stream);
+
+/* Visibility-masked Adam (csrc/post_opt.hip; gsplat's SelectiveAdam, simple_trainer.py:449-450), one launch per parameter tensor:
+ * p, g, m, v are f32 [U, M] (M floats per row), visible uint8 [U].  For every row with visible != 0 and every element of it
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;  p -= lr * m / (sqrt(v) + eps)
+ * with NO bias correction (there is no step argument).  A row with visible == 0 is not touched: its p, m, v are neither loaded
+ * nor stored and its g is NOT LOADED (a NaN there cannot reach a result) - the rows the mask clears belong to the caller, as the
+ * memory contract above says of skipped rows.  period / lr2 as in v3a_adam_step, the element index e taken within the whole
+ * tensor.  Arithmetic as v3a_adam_step: fp64 after the loads, one rounding at each store.  Thread t owns elements 4t .. 4t + 3
+ * of the flat tensor: 16-byte loads and stores where all four lie in visible rows, element by element where a visible and an
+ * invisible row meet, nothing where none is visible; a scalar tail (all scalar when a pointer is not 16-byte aligned). */
+typedef struct {
+  float* p; const float* g; float* m; float* v;
+  const uint8_t* visible;
+  long U; long M;
+  double lr, lr2;
+  int period;
+  double beta1, beta2, eps;
+} v3a_adam_visible_args;
+int v3a_adam_step_visible(const v3a_adam_visible_args* a, void* stream);
 
 /* The pose optimiser's parametrisation (csrc/post_opt.hip; post_opt/utils.py:12-48 CameraOptModule, :117-138): per camera 9
  * deltas (dx[3], drot[6]); a1 = drot[0..2] + (1,0,0), a2 = drot[3..5] + (0,1,0), b1 = a1 / max(|a1|, 1e-12),

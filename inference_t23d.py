@@ -67,7 +67,7 @@ def build_text_encoder(args, device):
 
 def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0.0, bilateral_grid=False, eval_every=0, lpips=None,
            antialiased=False, random_bkgd=False, opacity_reg=0.0, scale_reg=0.0, mcmc=None, pose_opt=False, pose_lr=None,
-           cameras_out=None, densify=None):
+           cameras_out=None, densify=None, batch_size=1, visible_adam=False):
     """-> (refined Gaussians, stats or None).  With eval_every = K > 0 the views with index % K == 0 are held out of the loop and
     scored before and after it: stats = {"before": {...}, "after": {...}, "held_out": [...]} (vist3a_amd.post_opt.evaluate_views).
     antialiased / random_bkgd / opacity_reg / scale_reg: the PostOptConfig fields of those names; the evaluation renders in the
@@ -76,7 +76,8 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
     default) - scene and cameras are refined together, and the dict `cameras_out` (if given) receives "extrinsics" (the adjusted
     camera-to-world matrix of every view, held-out views as given), "deltas" [Vt,9] and "train_views", as lists.
     densify: None, or densify_options' dict of PostOptConfig fields to run the loop with cfg.strategy = "densify" (adaptive density
-    control: clone / split / prune); the refined scene has as many Gaussians as it left."""
+    control: clone / split / prune); the refined scene has as many Gaussians as it left.
+    batch_size / visible_adam: the PostOptConfig fields of those names (views per step; the masked Adam update)."""
     from vist3a_amd import ops
     from vist3a_amd.post_opt import PostOptConfig, adjusted_extrinsics, create_splats, evaluate_views, post_optimize, train_views
     with torch.no_grad():
@@ -105,6 +106,7 @@ def refine(gaussians, clip_cl, pose, res, steps, depth_dict=None, depth_lambda=0
         for k, x in densify.items():
             setattr(cfg, k, x)
     cfg.pose_opt = bool(pose_opt)
+    cfg.batch_size, cfg.visible_adam = batch_size, bool(visible_adam)
     if pose_lr is not None:
         cfg.pose_opt_lr = float(pose_lr)
     ext, intr = pose["extrinsic"][0].detach(), pose["intrinsic"][0].detach()
@@ -146,6 +148,18 @@ def mcmc_options(args):
     return args.post_opt_mcmc_cap_max, refine_at
 
 
+def batch_options(args):
+    """--post_opt_batch_size / --post_opt_visible_adam -> (batch_size, visible_adam) for refine(), validated as PostOptConfig does"""
+    from vist3a_amd.post_opt import PostOptConfig
+    if (args.post_opt_batch_size != 1 or args.post_opt_visible_adam) and args.post_opt_steps <= 0:
+        raise ValueError("--post_opt_batch_size / --post_opt_visible_adam need --post_opt_steps > 0 (they are options of the post-optimisation)")
+    try:
+        PostOptConfig(batch_size=args.post_opt_batch_size, visible_adam=bool(args.post_opt_visible_adam)).check_batch()
+    except ValueError as e:
+        raise ValueError(f"--post_opt_batch_size: {e}") from None
+    return args.post_opt_batch_size, bool(args.post_opt_visible_adam)
+
+
 def densify_options(args):
     """--post_opt_densify* -> None (off) or the PostOptConfig fields of the "densify" strategy for refine()"""
     if not args.post_opt_densify:
@@ -171,6 +185,7 @@ def densify_options(args):
 
 
 def main(args):
+    batch_size, visible_adam = batch_options(args)   # before anything is loaded: a refused batch size costs nothing
     setup_dist()
     rank, world = dist.get_rank(), dist.get_world_size()
     device = torch.device(f"cuda:{rank % torch.cuda.device_count()}")
@@ -234,7 +249,8 @@ def main(args):
                               args.post_opt_depth_lambda, args.post_opt_bilateral_grid, args.post_opt_eval_every, lpips,
                               antialiased=args.post_opt_antialiased, random_bkgd=args.post_opt_random_bkgd,
                               opacity_reg=args.post_opt_opacity_reg, scale_reg=args.post_opt_scale_reg, mcmc=mcmc,
-                              pose_opt=args.post_opt_pose_opt, pose_lr=args.post_opt_pose_lr, cameras_out=cameras, densify=densify)
+                              pose_opt=args.post_opt_pose_opt, pose_lr=args.post_opt_pose_lr, cameras_out=cameras, densify=densify,
+                              batch_size=batch_size, visible_adam=visible_adam)
             if stats is not None:
                 (save / "post_opt_stats.json").write_text(json.dumps(stats, indent=1))
             if args.post_opt_pose_opt:   # the refined cameras; the videos below keep the predicted path, as the reference's trajectory does

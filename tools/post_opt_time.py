@@ -21,7 +21,11 @@ With --densify a further JSON line times the densification strategy (csrc/densif
 Gaussians: the per-step accumulate launch (28 B per Gaussian and camera) and one refine's entry points - classify (three launches:
 fates and block scans, block prefix, offsets), apply (two launches: the 11-float rows, the harmonics rows) with a third of the scene
 above the gradient threshold, and the opacity reset; the bytes apply moves over its time.  With --absgrad also the rasteriser's
-backward call without and with the absolute-gradient output (the ABS instantiations of its two kernels)."""
+backward call without and with the absolute-gradient output (the ABS instantiations of its two kernels).
+With --batch B and / or --visible_adam a further JSON line times the step as cfg.batch_size = B and cfg.visible_adam run it: B
+cameras (the tool's camera turned by 0.05 rad each) in one render, loss and backward, then the visibility mask and the five Adam
+launches (ops.adam_step_visible under --visible_adam): the Adam launches and the whole step, per step and per view.  It also times,
+tensor by tensor and at that step's mask, ops.adam_step_visible against ops.adam_step, next to the visible fraction."""
 import argparse
 import json
 import math
@@ -49,6 +53,8 @@ def main():
                          "compared (the harmonics' Adam launch alone moves by 7 %% with where its four 720 MB buffers lie)")
     ap.add_argument("--densify", action="store_true", help="also time the densification strategy's accumulate launch and the pieces of one refine")
     ap.add_argument("--absgrad", action="store_true", help="with --densify: also the rasteriser's backward without and with absgrad")
+    ap.add_argument("--batch", type=int, default=1, metavar="B", help="also time the step with B views per step (cfg.batch_size)")
+    ap.add_argument("--visible_adam", action="store_true", help="also time the step with the visibility-masked Adam (cfg.visible_adam)")
     a = ap.parse_args()
     if a.reserve_gb > 0:
         block = torch.empty(a.reserve_gb << 30, dtype=torch.uint8, device="cuda")
@@ -142,6 +148,8 @@ def main():
         print(json.dumps(mcmc_times(ops, {k: t.detach() for k, t in p.items()}, m, v, a.warmup, a.iters)))
     if a.densify:
         print(json.dumps(densify_times(ops, {k: t.detach() for k, t in p.items()}, m, v, view, campos, K, bg, ws, W, H, a.absgrad, a.warmup, a.iters)))
+    if a.batch > 1 or a.visible_adam:
+        print(json.dumps(batch_times(ops, p, m, v, K, bg, ws, W, H, a.batch, a.visible_adam, a.warmup, a.iters)))
     if a.pose_opt:
         print(json.dumps(pose_times(ops, p, view, K, target, bg, ws, W, H, "antialiased" if a.antialiased else "classic", a.warmup, a.iters)))
 
@@ -192,6 +200,74 @@ def densify_times(ops, p, m, v, view, campos, K, bg, ws, W, H, absgrad, warmup, 
     return dict(gaussians=U, size=W, visible=int((pr["radii"] > 0).sum()), absgrad=bool(absgrad), grow_grad2d=thr,
                 kept_cloned_split=totals, rows_after=U_out, accumulate_bytes=28 * U, accumulate_GBps=round(28 * U / timed["accumulate"] / 1e6, 1),
                 apply_bytes=moved, apply_GBps=round(moved / timed["apply"] / 1e6, 1), **{k + "_ms": round(x, 4) for k, x in timed.items()})
+
+
+def batch_times(ops, p, m, v, K, bg, ws, W, H, B, visible_adam, warmup, iters):
+    U = p["means"].shape[0]
+    views = []
+    for b in range(B):
+        yaw = -0.15 + 0.05 * b
+        vm = torch.eye(4)
+        vm[:3, :3] = torch.tensor([[math.cos(yaw), 0, math.sin(yaw)], [0, 1, 0], [-math.sin(yaw), 0, math.cos(yaw)]])
+        vm[:3, 3] = torch.tensor([0.1, -0.2, 0.3])
+        views.append(vm)
+    view = torch.stack(views)
+    campos = torch.linalg.inv(view)[:, :3, 3].contiguous().cuda()
+    view, Kb = view.cuda(), K.expand(B, 3, 3).contiguous()
+    target = torch.rand(B, H, W, 3, device="cuda")
+    r = math.sqrt(B)
+    betas, eps = (1 - B * 0.1, 1 - B * 0.001), 1e-15 / r
+    adam_ms, step_ms = [], []
+    for it in range(warmup + iters):
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        info = {}
+        col, _, _ = ops.gs_render(p["means"], cov, p["sh"], op, view, campos, Kb, W, H, background=bg, clamp_rgb=True, workspace=ws,
+                                  info_out=info if visible_adam else None)
+        loss, _, _ = ops.photometric_loss(col, target, 0.2)
+        grads = torch.autograd.grad(loss, list(p.values()))
+        e[1].record()
+        with torch.no_grad():
+            if visible_adam:
+                visible = ops.gs_visibility(info["radii"])
+            for (k, t), gr in zip(p.items(), grads):
+                two = dict(lr2=5e-5 * r, period=25) if k == "sh" else {}
+                if visible_adam:
+                    ops.adam_step_visible(t, gr, m[k], v[k], visible, lr=1e-3 * r, betas=betas, eps=eps, **two)
+                else:
+                    ops.adam_step(t, gr, m[k], v[k], lr=1e-3 * r, step=it + 1, betas=betas, eps=eps, **two)
+        e[2].record()
+        torch.cuda.synchronize()
+        if it >= warmup:
+            adam_ms.append(e[1].elapsed_time(e[2]))
+            step_ms.append(e[0].elapsed_time(e[2]))
+    a_ms, s_ms = statistics.median(adam_ms), statistics.median(step_ms)
+    # tensor by tensor at this batch's mask: the masked launch against the dense one
+    with torch.no_grad():
+        cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
+        visible = ops.gs_visibility(ops.gs_project(p["means"].detach(), cov, p["sh"].detach(), view, campos, Kb, W, H)["radii"])
+        ratios = {}
+        for k, t in p.items():
+            t, gr = t.detach().clone(), torch.randn_like(t)
+            two = dict(lr2=5e-5, period=25) if k == "sh" else {}
+            td, tv = [], []
+            for it in range(warmup + iters):
+                e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                e[0].record()
+                ops.adam_step(t, gr, m[k], v[k], lr=1e-3, step=it + 1, eps=1e-15, **two)
+                e[1].record()
+                ops.adam_step_visible(t, gr, m[k], v[k], visible, lr=1e-3, eps=1e-15, **two)
+                e[2].record()
+                torch.cuda.synchronize()
+                if it >= warmup:
+                    td.append(e[0].elapsed_time(e[1]))
+                    tv.append(e[1].elapsed_time(e[2]))
+            d_ms, v_ms = statistics.median(td), statistics.median(tv)
+            ratios[k] = dict(row_bytes=4 * t.numel() // U, adam_ms=round(d_ms, 4), adam_visible_ms=round(v_ms, 4), visible_over_dense=round(v_ms / d_ms, 3))
+    return dict(gaussians=U, size=W, batch=B, visible_adam=bool(visible_adam), visible_fraction=round(float(visible.float().mean()), 4),
+                adam_ms_per_step=round(a_ms, 3), adam_ms_per_view=round(a_ms / B, 3), step_ms_per_step=round(s_ms, 3),
+                step_ms_per_view=round(s_ms / B, 3), per_tensor=ratios)
 
 
 def pose_times(ops, p, view, K, target, bg, ws, W, H, mode, warmup, iters):

@@ -144,6 +144,71 @@ __global__ void __launch_bounds__(256) adam_kernel(const AdamP a) {
   }
 }
 
+// ---------------------------------------------------------------------------------------------- visibility-masked Adam
+// The step's visibility mask: one thread per Gaussian walks the cameras in index order; every byte is written once.
+__global__ void __launch_bounds__(256) gs_visibility_kernel(const int* __restrict__ radii, int C, long U, uint8_t* __restrict__ visible) {
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= U) return;
+  int seen = 0;
+  for (int c = 0; c < C; ++c) seen |= radii[(long)c * U + u] > 0;
+  visible[u] = (uint8_t)seen;
+}
+
+// gsplat's SelectiveAdam on rows of M floats: adam_kernel's flat map (thread t owns elements 4t .. 4t + 3 of the whole tensor, lane i
+// at base + 16 i, so a wave's accesses stay one contiguous KiB whatever M is), with the mask looked up per element.  A thread whose
+// four elements are all visible takes adam_kernel's 16-byte path; one with none returns before any load of p, g, m, v; a thread that
+// straddles a visible and an invisible row goes element by element, so that an invisible row is neither loaded nor stored.  The
+// arithmetic is adam_one with both bias corrections 1.
+__global__ void __launch_bounds__(256) adam_visible_kernel(const AdamP a, const uint8_t* __restrict__ visible, const long M) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t < a.nvec) {
+    const long e0 = t * 4;
+    long row = e0 / M;
+    long col = e0 - row * M;
+    bool vis[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      vis[e] = visible[row] != 0;
+      if (++col == M) { col = 0; ++row; }
+    }
+    const bool any = vis[0] | vis[1] | vis[2] | vis[3], all = vis[0] & vis[1] & vis[2] & vis[3];
+    if (!any) return;
+    double st[4];
+    const unsigned r0 = a.period > 0 ? (unsigned)(e0 % a.period) : 0u;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) st[e] = (a.period > 0 && (r0 + e) % (unsigned)a.period != 0) ? a.step2 : a.step1;
+    if (all) {
+      float4 p = ((const float4*)a.p)[t], m = ((const float4*)a.m)[t], v = ((const float4*)a.v)[t];
+      const float4 g = ((const float4*)a.g)[t];
+      adam_one(p.x, g.x, m.x, v.x, st[0], a);
+      adam_one(p.y, g.y, m.y, v.y, st[1], a);
+      adam_one(p.z, g.z, m.z, v.z, st[2], a);
+      adam_one(p.w, g.w, m.w, v.w, st[3], a);
+      ((float4*)a.p)[t] = p;
+      ((float4*)a.m)[t] = m;
+      ((float4*)a.v)[t] = v;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        if (!vis[e]) continue;
+        float p = a.p[e0 + e], m = a.m[e0 + e], v = a.v[e0 + e];
+        adam_one(p, a.g[e0 + e], m, v, st[e], a);
+        a.p[e0 + e] = p;
+        a.m[e0 + e] = m;
+        a.v[e0 + e] = v;
+      }
+    }
+  } else {            // scalar tail (and the whole tensor when a pointer is not 16-byte aligned)
+    const long e = a.nvec * 4 + (t - a.nvec);
+    if (e >= a.n || visible[e / M] == 0) return;
+    float p = a.p[e], m = a.m[e], v = a.v[e];
+    adam_one(p, a.g[e], m, v, (a.period > 0 && e % a.period != 0) ? a.step2 : a.step1, a);
+    a.p[e] = p;
+    a.m[e] = m;
+    a.v[e] = v;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------- camera pose deltas
 // The rotation of a 6D delta (utils.py:117-138): a1 = r[0..2] + (1,0,0), a2 = r[3..5] + (0,1,0); b1 = a1 / max(|a1|, 1e-12),
 // u = a2 - (b1 . a2) b1, b2 = u / max(|u|, 1e-12), b3 = b1 x b2.  Rd has the ROWS b1, b2, b3.
@@ -304,5 +369,33 @@ extern "C" int v3a_adam_step(const v3a_adam_args* a, void* stream) {
   const long threads = k.nvec + (a->n - 4 * k.nvec);
   if ((threads + 255) / 256 > 0x7fffffffL) return V3A_ERR_SHAPE;
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k);
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}
+
+extern "C" int v3a_gs_visibility(const int* radii, int C, long U, uint8_t* visible, void* stream) {
+  if (!radii || !visible) return V3A_ERR_ARG;
+  if (C < 1 || U < 1 || U > 0x7fffffffL * 256) return V3A_ERR_SHAPE;
+  hipLaunchKernelGGL(gs_visibility_kernel, dim3((unsigned)((U + 255) / 256)), dim3(256), 0, (hipStream_t)stream, radii, C, U, visible);
+  return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
+}
+
+extern "C" int v3a_adam_step_visible(const v3a_adam_visible_args* a, void* stream) {
+  if (!a || !a->p || !a->g || !a->m || !a->v || !a->visible) return V3A_ERR_ARG;
+  if (a->U < 1 || a->M < 1 || a->period < 0 || a->M > 0x7fffffffffffffffL / a->U) return V3A_ERR_SHAPE;
+  AdamP k;
+  k.p = a->p; k.g = a->g; k.m = a->m; k.v = a->v;
+  k.n = a->U * a->M;
+  const uintptr_t al = (uintptr_t)a->p | (uintptr_t)a->g | (uintptr_t)a->m | (uintptr_t)a->v;
+  k.nvec = (al & 15) ? 0 : k.n / 4;
+  k.period = a->period;
+  k.b1 = a->beta1;
+  k.b2 = a->beta2;
+  k.step1 = a->lr;      // no bias correction: both are 1
+  k.step2 = a->lr2;
+  k.inv_sqrt_bc2 = 1.f;
+  k.eps = (float)a->eps;
+  const long threads = k.nvec + (k.n - 4 * k.nvec);
+  if ((threads + 255) / 256 > 0x7fffffffL) return V3A_ERR_SHAPE;
+  hipLaunchKernelGGL(adam_visible_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream, k, a->visible, a->M);
   return hipGetLastError() == hipSuccess ? V3A_OK : V3A_ERR_LAUNCH;
 }

@@ -306,6 +306,16 @@ class AdamArgs(C.Structure):
     ]
 
 
+class AdamVisibleArgs(C.Structure):
+    _fields_ = [
+        ("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
+        ("visible", C.c_void_p),
+        ("U", C.c_long), ("M", C.c_long),
+        ("lr", C.c_double), ("lr2", C.c_double), ("period", C.c_int),
+        ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+    ]
+
+
 # the C field names of a scene's five tensors, in the order of ops.SPLAT_TENSORS
 SPLAT_FIELDS = ("means", "log_scales", "quats", "logits", "sh")
 
@@ -458,6 +468,8 @@ SYMBOLS = {
     "v3a_splat_activate": (C.c_int, [C.c_void_p] * 3 + [C.c_long] + [C.c_void_p] * 3),
     "v3a_splat_activate_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_long] + [C.c_void_p] * 4),
     "v3a_adam_step": (C.c_int, [C.POINTER(AdamArgs), C.c_void_p]),
+    "v3a_gs_visibility": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_void_p, C.c_void_p]),
+    "v3a_adam_step_visible": (C.c_int, [C.POINTER(AdamVisibleArgs), C.c_void_p]),
     "v3a_camera_adjust": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3),
     "v3a_camera_adjust_backward": (C.c_int, [C.c_void_p] * 5 + [C.c_int] + [C.c_void_p] * 2),
     "v3a_splat_reg_workspace_bytes": (C.c_long, [C.c_long]),
@@ -490,7 +502,7 @@ SYMBOLS = {
 }
 
 _lib = None
-EXPECTED_ABI = 35  # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 36  # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

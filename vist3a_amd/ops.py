@@ -1848,6 +1848,40 @@ def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor
     L.check(L.load().v3a_adam_step(C.byref(a), _stream()), "v3a_adam_step")
 
 
+def gs_visibility(radii: torch.Tensor) -> torch.Tensor:
+    """The step's visibility mask (simple_trainer.py:1111): radii int32 [C,U] as gs_render's info_out holds them -> uint8 [U], 1
+    where radii[c,g] > 0 for some camera c: (radii > 0).any(0) in one launch (v3a_gs_visibility), every byte written once."""
+    if radii.dim() != 2 or radii.shape[0] < 1:
+        raise ValueError(f"gs_visibility: radii [C,U] with C >= 1 required, got {tuple(radii.shape)}")
+    Cn, U = radii.shape
+    _i32_dev(radii, "radii", (Cn, U))
+    visible = torch.empty(U, device=radii.device, dtype=torch.uint8)
+    if U > 0:
+        L.check(L.load().v3a_gs_visibility(_ptr(radii), Cn, U, _ptr(visible), _stream()), "v3a_gs_visibility")
+    return visible
+
+
+def adam_step_visible(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, visible: torch.Tensor, *, lr: float,
+                      betas=(0.9, 0.999), eps: float = 1e-8, lr2: Optional[float] = None, period: int = 0) -> None:
+    """gsplat's SelectiveAdam (the reference's visible_adam, simple_trainer.py:449-450) on p, g, m, v f32 [U, ...] and the mask
+    `visible` uint8 [U] (gs_visibility), in place on p, m, v: every element of a row with visible != 0 gets
+    m = b1 m + (1 - b1) g, v = b2 v + (1 - b2) g^2, p -= lr m / (sqrt(v) + eps) - no bias correction, hence no step argument.  A
+    row with visible == 0 keeps the bits of p, m, v, and its g is not loaded (a NaN there reaches nothing).  period / lr2 as in
+    adam_step, the element index taken within the whole tensor."""
+    if p.dim() < 1 or p.shape[0] < 1 or p.numel() < 1:
+        raise ValueError(f"adam_step_visible: p [U, ...] with at least one element required, got {tuple(p.shape)}")
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        _f32_dev(t, name, p.shape)
+    U = p.shape[0]
+    if not isinstance(visible, torch.Tensor) or not visible.is_cuda or visible.device != p.device or visible.dtype != torch.uint8 \
+            or not visible.is_contiguous() or tuple(visible.shape) != (U,):
+        raise ValueError(f"visible must be a contiguous uint8 tensor of shape {(U,)} on {p.device}, got "
+                         f"{getattr(visible, 'dtype', type(visible))} {tuple(getattr(visible, 'shape', ()))} on {getattr(visible, 'device', None)}")
+    a = L.AdamVisibleArgs(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(visible), U, p.numel() // U, float(lr), float(lr if lr2 is None else lr2),
+                          int(period), float(betas[0]), float(betas[1]), float(eps))
+    L.check(L.load().v3a_adam_step_visible(C.byref(a), _stream()), "v3a_adam_step_visible")
+
+
 # the random streams of the strategies' Philox draws: the sampler's two (2 and 3 are the noise's draws), and the first of the two
 # consecutive streams of each split child of the densification (z0, z1 of stream s, z2 = z0 of stream s + 1)
 MCMC_STREAMS = dict(relocate=0, grow=1, split0=4, split1=6)

@@ -44,12 +44,19 @@ cfg.densify_grow_grad2d are cloned (small ones) or split in two (large ones), tr
 (ops.densify_reset_opacity).  One read-back per refine - the three segment sizes, which size the new tensors (gsplat syncs there
 too) - and a second one only when cfg.densify_cap_max turns a refine into prune-only.
 
+cfg.batch_size = B > 1 is the reference's batch_size (:268, :848-855): every step shows a batch of up to B distinct views
+(train_batch_order) to ONE render, loss and backward - every op of the step takes a leading camera or image dimension - and updates
+once, with the optimisers scaled as the reference scales them (batch_hyperparameters; :441-461, :660, :707).  cfg.visible_adam is
+its visible_adam (:322, :449-450, :1103-1116; gsplat's SelectiveAdam, restated in DESIGN.md section 7f): ops.gs_visibility turns the
+render's radii into the step's mask and ops.adam_step_visible updates only the Gaussians some view of the step saw, without bias
+correction; the others keep parameters and moments.  With both at their defaults the loop is what it was.
+
 The harmonics stay ONE [U,3,K] tensor: the reference's sh0 / shN optimisers (rates lr_sh and lr_sh / 20) are one ops.adam_step with
 a period of K, which is the same arithmetic because Adam is elementwise."""
 from __future__ import annotations
 
 from dataclasses import dataclass
-from math import isqrt
+from math import isqrt, sqrt
 from typing import Optional, Tuple
 
 import torch
@@ -78,7 +85,7 @@ class PostOptConfig:
     scene_scale: float = 1.0         # multiplies the depth term (:426, :960)
     use_bilateral_grid: bool = False                        # :352-355
     bilateral_grid_shape: Tuple[int, int, int] = (16, 16, 8)   # (X, Y, W = the guidance axis L), as the reference spells it
-    bilagrid_lr: float = 2e-3        # :707, times sqrt(batch_size) = 1
+    bilagrid_lr: float = 2e-3        # :707, times sqrt(batch_size)
     bilagrid_warmup_steps: int = 1000   # :839: LinearLR(0.01 -> 1) chained with the decay to 1 % over max_steps
     bilagrid_tv_lambda: float = 10.0    # :963
     antialiased: bool = False        # :323-324: rasterize_mode="antialiased" (the loop's renders; evaluation and export follow it)
@@ -109,6 +116,8 @@ class PostOptConfig:
     pose_opt: bool = False           # :335-336; True in the reference - off here so that existing calls keep their bits (a stated deviation)
     pose_opt_lr: float = 1e-5        # :337
     pose_opt_reg: float = 1e-6       # :338: the pose Adam's weight decay
+    batch_size: int = 1              # :268: views per step (1 .. 9); rates, eps and betas scale with it (batch_hyperparameters)
+    visible_adam: bool = False       # :322: gsplat's SelectiveAdam - only the Gaussians some view of the step saw are updated
     # ours
     params: Tuple[str, ...] = ("means", "scales", "quats", "opacities", "sh0", "shN")
     seed: int = 0
@@ -173,6 +182,18 @@ class PostOptConfig:
         if not isinstance(self.max_steps, int) or self.max_steps < 1:
             raise ValueError(f"PostOptConfig.max_steps must be a positive integer (the pose rate decays over it), got {self.max_steps!r}")
 
+    def check_batch(self) -> None:
+        B = self.batch_size
+        if isinstance(B, bool) or not isinstance(B, int) or B < 1:
+            raise ValueError(f"PostOptConfig.batch_size must be an integer >= 1, got {B!r}")
+        if B >= 10:
+            raise ValueError(f"PostOptConfig.batch_size must be at most 9, got {B!r}: the reference sets beta1 = 1 - batch_size * (1 - 0.9), "
+                             "which is 0 at 10 and negative beyond - a case the reference itself leaves unresolved")
+        if not isinstance(self.visible_adam, bool):
+            raise ValueError(f"PostOptConfig.visible_adam must be a bool, got {self.visible_adam!r}")
+        if B > 1 and not all(0.0 <= 1.0 - B * (1.0 - b) < 1.0 for b in self.betas):
+            raise ValueError(f"PostOptConfig.betas = {tuple(self.betas)!r} leave [0, 1) at batch_size = {B}: 1 - batch_size * (1 - beta)")
+
     def check_bilagrid(self) -> None:
         if not self.use_bilateral_grid:
             return
@@ -196,6 +217,21 @@ def bilagrid_learning_rate(cfg: PostOptConfig, s: int) -> float:
 def pose_learning_rate(cfg: PostOptConfig, s: int) -> float:
     """The pose Adam's rate at the step with `s` earlier steps: ExponentialLR(0.01 ** (1 / max_steps)) in closed form (:824-829)."""
     return cfg.pose_opt_lr * (0.01 ** (s / cfg.max_steps))
+
+
+def batch_hyperparameters(cfg: PostOptConfig) -> dict:
+    """The reference's scaling of the optimisers with B = cfg.batch_size (:441-461, :660, :707) -> dict(lr = {tensor: its rate times
+    sqrt(B)} for the five splat tensors (the means' decay multiplies it per step), eps = cfg.eps / sqrt(B), betas = (1 - B (1 - b1),
+    1 - B (1 - b2)), lr_scale = sqrt(B): what the bilateral-grid and pose rates are multiplied by, their eps and betas staying).
+    B is the configured size, never the length of an epoch's short last batch.  At B = 1 nothing is multiplied or divided: the
+    values are cfg's own, lr_scale is 1.0."""
+    B = cfg.batch_size
+    lr = dict(means=cfg.lr_means, scales=cfg.lr_scales, quats=cfg.lr_quats, opacities=cfg.lr_opacities, sh=cfg.lr_sh)
+    if B == 1:
+        return dict(lr=lr, eps=cfg.eps, betas=(cfg.betas[0], cfg.betas[1]), lr_scale=1.0)
+    r = sqrt(B)
+    return dict(lr={n: x * r for n, x in lr.items()}, eps=cfg.eps / r,
+                betas=(1.0 - B * (1.0 - cfg.betas[0]), 1.0 - B * (1.0 - cfg.betas[1])), lr_scale=r)
 
 
 def view_order(n_views: int, steps: int, seed: int) -> list:
@@ -352,6 +388,23 @@ def train_view_order(n_views: int, steps: int, seed: int, test_every: int = 0) -
     return [train[j] for j in view_order(len(train), steps, seed)]
 
 
+def train_batch_order(n_views: int, steps: int, seed: int, test_every: int = 0, batch_size: int = 1) -> list:
+    """The views of every step of post_optimize, a list of `steps` lists: view_order's per-epoch permutations of the training views
+    (same generator, same seed), each cut into consecutive chunks of batch_size; an epoch's last chunk is short when batch_size does
+    not divide the number of training views (DataLoader(shuffle=True, drop_last=False), :848-855).  The views of a batch are
+    distinct.  With batch_size = 1 it is [[j] for j in train_view_order(...)]."""
+    B = int(batch_size)
+    if B < 1:
+        raise ValueError(f"train_batch_order: batch_size must be >= 1, got {batch_size!r}")
+    train = train_views(n_views, test_every)
+    g = torch.Generator().manual_seed(int(seed))
+    out = []
+    while len(out) < steps:
+        perm = torch.randperm(len(train), generator=g).tolist()
+        out += [[train[j] for j in perm[k:k + B]] for k in range(0, len(perm), B)]
+    return out[:steps]
+
+
 def _single(gaussians: Gaussians) -> None:
     if gaussians.means.dim() != 3 or gaussians.means.shape[0] != 1:
         raise ValueError(f"post-optimisation takes one scene (batch dimension 1), got means of shape {tuple(gaussians.means.shape)}")
@@ -497,6 +550,12 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     `extrinsics` that require grad are still refused: the deltas are the loop's own state.  adjusted_extrinsics(extrinsics, splats,
     cfg) returns the refined cameras; held-out views keep their given poses.  The log has no column of its own for it.
 
+    With cfg.batch_size = B > 1 a step shows the views train_batch_order(V, steps, cfg.seed, cfg.test_every, B)[i] - up to B distinct
+    views, fewer in an epoch's last batch - to one render, one loss (the means run over the batch), one backward and one update with
+    batch_hyperparameters(cfg); one random background per step; the log keeps one row per step and splats["step"] counts steps.
+    With cfg.visible_adam the five splat tensors update through ops.adam_step_visible under ops.gs_visibility(the step's radii):
+    rows no view of the step saw keep parameters and moments; grids and pose deltas keep ops.adam_step.
+
     With cfg.strategy = "densify", after the Adam updates of 0-based step i (while densify_active_at(cfg, i)): ops.densify_accumulate
     adds the step's screen-space gradients (gs_render's info_out; the absolute ones with cfg.densify_absgrad) to splats["densify"] =
     {"grad2d": f32 [U], "count": int32 [U]}; if densify_refines_at(cfg, i), densify_refine (the tensors in `splats` are replaced, the
@@ -509,6 +568,7 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     cfg.check_bilagrid()
     cfg.check_strategy()
     cfg.check_pose()
+    cfg.check_batch()
     _single(gaussians)
     for t, n in ((extrinsics, "extrinsics"), (intrinsics, "intrinsics")):
         if t.requires_grad:
@@ -566,37 +626,45 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
     mode = "antialiased" if cfg.antialiased else "classic"
     reg_op, reg_sc = cfg.opacity_reg > 0.0, cfg.scale_reg > 0.0
     log = torch.zeros(steps, len(log_columns(cfg)), device=dev, dtype=torch.float64)
-    lrs = dict(means=cfg.lr_means, scales=cfg.lr_scales, quats=cfg.lr_quats, opacities=cfg.lr_opacities, sh=cfg.lr_sh)
+    hyp = batch_hyperparameters(cfg)
+    lrs, lr_scale = hyp["lr"], hyp["lr_scale"]
+    vis_adam = cfg.visible_adam
     decay = 0.01 ** (1.0 / cfg.max_steps)
     ws = ops.GsWorkspace()
     mcmc = cfg.strategy == "mcmc"
     densify = cfg.strategy == "densify"
     if densify:
         densify_state(splats)
-    extra = dict(info_out={}, absgrad=cfg.densify_absgrad) if densify else {}    # what the densification reads of every render
+    # what the densification and the visibility mask read of every render
+    extra = dict(info_out={}, absgrad=cfg.densify_absgrad) if densify else dict(info_out={}) if vis_adam else {}
     leaves = [p[n].requires_grad_(True) for n in trained]
     if bil:
         leaves.append(splats["bil_grids"].requires_grad_(True))
     if pose:   # the last leaf; its gradient is dense [Vt,9] with zero rows for the other views, as nn.Embedding's is
         leaves.append(splats["pose_deltas"].requires_grad_(True))
     try:
-        for i, j in enumerate(train_view_order(V, steps, cfg.seed, cfg.test_every)):
+        for i, js in enumerate(train_batch_order(V, steps, cfg.seed, cfg.test_every, cfg.batch_size)):
+            if len(js) == 1:     # one view: slices (views of the tensors, no copy)
+                j = slice(js[0], js[0] + 1)
+                gj = slice(grid_of[js[0]], grid_of[js[0]] + 1)
+            else:                # b distinct views: gathered rows; the gradient's scatter back is order-free
+                j = torch.tensor(js, device=dev)
+                gj = torch.tensor([grid_of[x] for x in js], device=dev)
             cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
             if pose:
-                g_ = grid_of[j]
-                view_j, campos_j = ops.camera_adjust(w2c_base[j:j + 1], c2w_base[j:j + 1], splats["pose_deltas"][g_:g_ + 1])
-                color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view_j, campos_j, Kpix[j:j + 1], W, H,
+                view_j, campos_j = ops.camera_adjust(w2c_base[j], c2w_base[j], splats["pose_deltas"][gj])
+                color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view_j, campos_j, Kpix[j], W, H,
                                             sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
                                             clamp_rgb=True, workspace=ws, rasterize_mode=mode, camera_grad=True, **extra)
             else:
-                color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j:j + 1], campos[j:j + 1], Kpix[j:j + 1], W, H,
+                color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j], campos[j], Kpix[j], W, H,
                                             sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
                                             clamp_rgb=True, workspace=ws, rasterize_mode=mode, **extra)
             if bil:
-                color = ops.bilagrid_slice(color, splats["bil_grids"][grid_of[j]:grid_of[j] + 1])
-            loss, l1, ssim = ops.photometric_loss(color, images[j:j + 1], cfg.ssim_lambda)
+                color = ops.bilagrid_slice(color, splats["bil_grids"][gj])
+            loss, l1, ssim = ops.photometric_loss(color, images[j], cfg.ssim_lambda)
             if cfg.depth_loss:
-                dterm, _ = ops.depth_loss(depth, alpha, depths[j:j + 1], None if depth_masks is None else depth_masks[j:j + 1], cfg.scene_scale)
+                dterm, _ = ops.depth_loss(depth, alpha, depths[j], None if depth_masks is None else depth_masks[j], cfg.scene_scale)
                 loss = loss + cfg.depth_lambda * dterm
                 rec = [loss.detach(), l1.detach(), ssim.detach(), dterm.detach()]
             else:
@@ -618,23 +686,31 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
             log[i].copy_(torch.stack(rec))
             t = splats["step"] + 1
             with torch.no_grad():
+                if vis_adam:   # the Gaussians some view of this step saw (:1111)
+                    visible = ops.gs_visibility(extra["info_out"]["radii"])
                 for n, g in zip(trained, grads):
                     lr = lrs[n] * (decay ** (t - 1) if n == "means" else 1.0)
                     sh = n == "sh"
-                    ops.adam_step(p[n], g.contiguous(), m[n], v[n], lr=lr, step=t, betas=cfg.betas, eps=cfg.eps,
-                                  lr2=lr / 20 if sh else None, period=Ksh if sh and Ksh > 1 else 0)
+                    if vis_adam:
+                        ops.adam_step_visible(p[n], g.contiguous(), m[n], v[n], visible, lr=lr, betas=hyp["betas"], eps=hyp["eps"],
+                                              lr2=lr / 20 if sh else None, period=Ksh if sh and Ksh > 1 else 0)
+                    else:
+                        ops.adam_step(p[n], g.contiguous(), m[n], v[n], lr=lr, step=t, betas=hyp["betas"], eps=hyp["eps"],
+                                      lr2=lr / 20 if sh else None, period=Ksh if sh and Ksh > 1 else 0)
                 if bil:   # every view's grid moves each step through the TV term, as in the reference
+                    lr = bilagrid_learning_rate(cfg, t - 1)
                     ops.adam_step(splats["bil_grids"], grads[len(trained)].contiguous(), splats["bil_m"], splats["bil_v"],
-                                  lr=bilagrid_learning_rate(cfg, t - 1), step=t, betas=cfg.betas, eps=1e-15, period=0)
+                                  lr=lr * lr_scale if lr_scale != 1.0 else lr, step=t, betas=cfg.betas, eps=1e-15, period=0)
                 if pose:  # torch.optim.Adam(weight_decay=reg): the decay joins the gradient; momentum and decay move every row each step
                     d = splats["pose_deltas"]
+                    lr = pose_learning_rate(cfg, t - 1)
                     ops.adam_step(d, (grads[-1] + cfg.pose_opt_reg * d).contiguous(), splats["pose_m"], splats["pose_v"],
-                                  lr=pose_learning_rate(cfg, t - 1), step=t, betas=(0.9, 0.999), eps=1e-8, period=0)
+                                  lr=lr * lr_scale if lr_scale != 1.0 else lr, step=t, betas=(0.9, 0.999), eps=1e-8, period=0)
                 if mcmc:
                     if mcmc_refines_at(cfg, t - 1):
                         mcmc_refine(splats, cfg, t)
                         leaves = [p[n].requires_grad_(True) for n in trained] + leaves[len(trained):]    # a grown scene has new tensors
-                    ops.mcmc_noise(p["means"], p["scales"], p["quats"], p["opacities"], scaler=cfg.mcmc_noise_lr * (cfg.lr_means * decay ** t),
+                    ops.mcmc_noise(p["means"], p["scales"], p["quats"], p["opacities"], scaler=cfg.mcmc_noise_lr * (lrs["means"] * decay ** t),
                                    seed=cfg.seed, step=t)
                 if densify and densify_active_at(cfg, t - 1):
                     info, st = extra["info_out"], densify_state(splats)

@@ -88,6 +88,12 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
                         "post_opt_cameras.json next to gaussians.ply (the videos keep the predicted path)")
     g.add_argument("--post_opt_pose_lr", type=float, default=None, metavar="X",
                    help="with --post_opt_pose_opt: the pose optimiser's learning rate (the reference's pose_opt_lr, 1e-5)")
+    g.add_argument("--post_opt_batch_size", type=int, default=1, metavar="B",
+                   help="views per post-optimisation step (the reference's batch_size), 1 to 9: one render, loss and backward over B views, "
+                        "one optimiser step; the rates are multiplied by sqrt(B), eps divided by it, the betas become 1 - B (1 - beta)")
+    g.add_argument("--post_opt_visible_adam", action="store_true",
+                   help="update only the Gaussians some view of the step saw (the reference's visible_adam, gsplat's SelectiveAdam: no "
+                        "bias correction; rows outside every view keep parameters and moments)")
     g.add_argument("--post_opt_eval_every", type=int, default=0, metavar="K",
                    help="hold the views with index %% K == 0 out of the post-optimisation (the reference's test_every) and evaluate them "
                         "before and after it: PSNR, SSIM, the number of Gaussians and a time per image - with --post_opt_bilateral_grid "
