@@ -38,7 +38,7 @@ extern "C" {
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 36) */
+int v3a_abi_version(void);            /* bumps whenever a signature changes (currently 37) */
 const char* v3a_build_info(void);     /* "gfx950 <date> <compiler>" */
 
 /* ------------------------------------------------------------------------------------------------
@@ -1081,6 +1081,44 @@ long v3a_splat_import_workspace_bytes(long n);   /* V3A_ERR_SHAPE for n < 0 or n
 int v3a_splat_import_ply(const v3a_splat_import_args* a, void* stream);
 int v3a_splat_import_compressed(const v3a_splat_import_args* a, void* stream);
 int v3a_splat_import_splat(const v3a_splat_import_args* a, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Similarity transforms of a scene (csrc/splat_transform.hip): x' = scale R x + t.  DESIGN.md section 7i states the contract.
+ *
+ * v3a_splat_transform: input and output scene as above (means, log-scales, quaternions, logits, harmonics f32 [rows,3,K+1]; ld_* /
+ *   out_ld_*: row strides in ELEMENTS; quats_xyzw holds for both).  K + 1 must be 1, 4, 9, 16 or 25 (whole bands up to degree 4).
+ *   Per row: mean' = (scale R) mean + t in fp32 (fmaf chain, last element first, on the fp32 roundings of scale R and t);
+ *   log-scale' = log-scale + (float)log(scale); quat' = q_R (x) quat (Hamilton product; q_R from R in fp64, w >= 0; not
+ *   renormalised); logit and band 0 copied; band l = 1..deg of every channel c' = D_l(R) c with Y_l(R d) = D_l(R) Y_l(d) in the
+ *   rasteriser's basis (sh_eval), D_l from fp64 rounded to fp32.  out == in with equal strides is allowed (a wave reads its 64
+ *   rows whole before it writes); any other overlap is the caller's error.  No atomics, no workspace.
+ *   Refusals, before any pointer is read: null struct V3A_ERR_ARG; rows < 0 or >= 2^31, K < 0 V3A_ERR_SHAPE; (rows > 0) a null
+ *   input V3A_ERR_ARG, a short input stride V3A_ERR_SHAPE; K + 1 not a band count V3A_ERR_SHAPE; scale not in (0, inf),
+ *   |R R^T - I|_max > 1e-6, det R <= 0 or a non-finite t V3A_ERR_ARG; then the outputs as the inputs.  rows == 0 launches nothing.
+ * v3a_sh_rotation_matrices: host only.  out f64 [sum_{l=1..deg} (2l+1)^2]: D_1 .. D_deg, each row-major, one after the other;
+ *   0 <= deg <= 4 (V3A_ERR_SHAPE), R as above (V3A_ERR_ARG).  D_l(I) = I exactly.
+ * v3a_splat_moments: out f64 [10] on the device = n, sum (x - c) [3], sum (x - c)(x - c)^T as xx xy xz yy yz zz, over the n rows
+ *   of means (row stride ld_means >= 3 elements), c = centre f64 [3] on the HOST.  fp64; a lane adds its 4 rows of a 1024-row tile
+ *   in index order, block_sum<256> of csrc/fixed_sum.h, then one workgroup adds the tiles in the same way: no atomics,
+ *   bit-identical run to run and for every ld_means.  workspace: v3a_splat_moments_workspace_bytes(n), 8-byte aligned.  n == 0
+ *   writes ten zeros.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float *means, *log_scales, *quats, *logits, *sh;
+  long ld_means, ld_log_scales, ld_quats, ld_logits, ld_sh;
+  float *out_means, *out_log_scales, *out_quats, *out_logits, *out_sh;
+  long out_ld_means, out_ld_log_scales, out_ld_quats, out_ld_logits, out_ld_sh;
+  long rows;
+  int K, quats_xyzw;
+  double scale;
+  double R[9];      /* row-major */
+  double t[3];
+} v3a_splat_transform_args;
+int v3a_splat_transform(const v3a_splat_transform_args* a, void* stream);
+int v3a_sh_rotation_matrices(const double* R, int deg, double* out);
+long v3a_splat_moments_workspace_bytes(long n);   /* V3A_ERR_SHAPE for n < 0 or n >= 2^31 */
+int v3a_splat_moments(const float* means, long ld_means, long n, const double* centre, double* out, void* workspace,
+                      long workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -28,6 +28,7 @@ from vist3a_amd.utils.argument import inference_vist3a_argument  # noqa: E402
 from vist3a_amd.utils.dist_util import setup_dist, shard_prompts  # noqa: E402
 from vist3a_amd.utils.ply_export import export_ply  # noqa: E402
 from vist3a_amd.utils.splat_export import FILE_NAMES as EXPORT_FILE_NAMES, export_gaussians, parse_formats as parse_export_formats  # noqa: E402
+from vist3a_amd.utils.splat_transform import transform_gaussians, world_normalisation, write_world_transform  # noqa: E402
 from vist3a_amd.wan.dit import WAN_1_3B, WAN_14B, WanDiT  # noqa: E402
 from vist3a_amd.wan.weights import load_dit_config, load_dit_state_dict, load_peft_lora, random_dit_state_dict  # noqa: E402
 
@@ -243,8 +244,8 @@ def main(args):
         os.makedirs(save, exist_ok=args.overwrite)  # the reference raises when the directory exists (inference_t23d.py:126)
         (save / "prompt.txt").write_text(prompt)
         g = out.gaussians
+        cameras = {}
         if args.post_opt_steps > 0:   # against the frames the reconstruction saw, at the predicted context poses and intrinsics
-            cameras = {}
             g, stats = refine(g, clip_cl, out.pred_context_pose, args.feedforward_resolution, args.post_opt_steps, out.depth_dict,
                               args.post_opt_depth_lambda, args.post_opt_bilateral_grid, args.post_opt_eval_every, lpips,
                               antialiased=args.post_opt_antialiased, random_bkgd=args.post_opt_random_bkgd,
@@ -265,6 +266,11 @@ def main(args):
                                         args.feedforward_resolution, g, str(save), decoder)
             finally:
                 decoder.rasterize_mode = mode
+        if args.export_frame == "normalized":   # the files below in the normalised world frame; the videos above kept the camera frame
+            ext = torch.tensor(cameras["extrinsics"], dtype=torch.float64) if "extrinsics" in cameras else out.pred_context_pose["extrinsic"][0]
+            T = world_normalisation(ext, g.means[0].detach().float().contiguous())
+            g = transform_gaussians(g, T)
+            write_world_transform(save / "world_transform.json", T, ext)
         export_ply(g.means[0], g.scales[0], g.rotations[0], g.harmonics[0], g.opacities[0], save / "gaussians.ply", save_sh_dc_only=True)
         for fmt in export_formats:   # extra files only: gaussians.ply above is written as without the flag
             export_gaussians(g, save / EXPORT_FILE_NAMES[fmt], fmt, sh_rest=args.export_sh_rest)

@@ -19,7 +19,7 @@ typedef __attribute__((ext_vector_type(8))) int i32x8;         // 32 e4m3 = one 
 #define V3A_ERR_LAUNCH (-3)
 #define V3A_ERR_WORKSPACE (-4)
 
-// Host-side one-liners of the entry points in mcmc.hip, densify.hip, splat_export.hip, splat_import.hip, voxel.hip and the rasteriser (gs_raster.h).
+// Host-side one-liners of the entry points in mcmc.hip, densify.hip, splat_export.hip, splat_import.hip, splat_transform.hip, voxel.hip and the rasteriser (gs_raster.h).
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }                // the pieces of a workspace start 256 bytes apart
 inline long blocks_for(long n, int threads) { return (n + threads - 1) / threads; }   // workgroups of `threads` lanes that cover n items
 inline bool bad_count(long n) { return n < 0 || n > 0x7fffffffL; }                   // a row count that int32 indices cannot hold

@@ -1,9 +1,9 @@
 // The one definition of reduction order for the fp64 loss / metric kernels (image_metrics, ssim_loss, lpips, clip, depth_loss,
 // bilagrid, color_correct, splat_reg), for the block totals of the MCMC sampler (mcmc) and for the camera-gradient finish of the
-// rasteriser's backward (raster_bwd), and - on integers - for the count of non-finite rows of a workgroup of the scene import
-// (splat_import): what their "no atomics, fixed order, bit-identical run to run" rests on.
+// rasteriser's backward (raster_bwd), for the moments of the principal-axes step (splat_transform), and - on integers - for the
+// count of non-finite rows of a workgroup of the scene import (splat_import): what their "no atomics, fixed order, bit-identical run to run" rests on.
 // tests/test_fixed_sum_gpu.py pins the order bit for bit (and tests/test_mcmc_gpu.py holds the sampler to a host emulation of
-// it).  Included by those eleven files only, not by common.h.
+// it).  Included by those twelve files only, not by common.h.
 //
 // Deliberately NOT built on these helpers, because moving them onto the tree would change bits: the batched trees of
 // cc_accumulate_kernel (11 wide) and bilagrid_slice_bwd_grid_kernel (12 wide), the single-thread sequential finishes

@@ -1,6 +1,6 @@
 // A scene as the strategy and file kernels handle it, stated once: the order of its five tensors, the floats in a row of each, the
-// strided view of splat_export.hip and splat_import.hip with its validation, and the contiguous parameter / moment sets of
-// mcmc.hip and densify.hip.  Included by those four files only, after common.h.
+// strided view of splat_export.hip, splat_import.hip and splat_transform.hip with its validation, and the contiguous parameter /
+// moment sets of mcmc.hip and densify.hip.  Included by those five files only, after common.h.
 #pragma once
 
 enum { SPLAT_MEANS, SPLAT_LS, SPLAT_QUATS, SPLAT_LOGITS, SPLAT_SH, SPLAT_FIELDS };   // the order in every struct of vist3a_hip.h
@@ -28,7 +28,7 @@ struct SplatView {
   __device__ int quat_slot(int e) const { return xyzw ? (e + 3) & 3 : e; }   // where component e of the files' order (w x y z) is stored
 };
 
-// The view of v3a_splat_export_args or v3a_splat_import_args (the same field names): V3A_OK - with v left alone when there are no
+// The view of v3a_splat_export_args, v3a_splat_import_args or either half of v3a_splat_transform_args (the same field names): V3A_OK - with v left alone when there are no
 // rows - or the error code, after which v means nothing.  No pointer is read through.
 template <class Args, class T>
 int splat_view_of(const Args* a, long rows, int K, SplatView<T>& v) {

@@ -380,6 +380,17 @@ class SplatImportArgs(C.Structure):
     )
 
 
+class SplatTransformArgs(C.Structure):
+    _fields_ = (
+        [(f, C.c_void_p) for f in SPLAT_FIELDS]
+        + [("ld_" + f, C.c_long) for f in SPLAT_FIELDS]
+        + [("out_" + f, C.c_void_p) for f in SPLAT_FIELDS]
+        + [("out_ld_" + f, C.c_long) for f in SPLAT_FIELDS]
+        + [("rows", C.c_long), ("K", C.c_int), ("quats_xyzw", C.c_int),
+           ("scale", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3)]
+    )
+
+
 # name -> (restype, argtypes); every symbol include/vist3a_hip.h declares must be listed here
 SYMBOLS = {
     "v3a_abi_version": (C.c_int, []),
@@ -499,10 +510,14 @@ SYMBOLS = {
     "v3a_splat_import_ply": (C.c_int, [C.POINTER(SplatImportArgs), C.c_void_p]),
     "v3a_splat_import_compressed": (C.c_int, [C.POINTER(SplatImportArgs), C.c_void_p]),
     "v3a_splat_import_splat": (C.c_int, [C.POINTER(SplatImportArgs), C.c_void_p]),
+    "v3a_splat_transform": (C.c_int, [C.POINTER(SplatTransformArgs), C.c_void_p]),
+    "v3a_sh_rotation_matrices": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double)]),
+    "v3a_splat_moments_workspace_bytes": (C.c_long, [C.c_long]),
+    "v3a_splat_moments": (C.c_int, [C.c_void_p, C.c_long, C.c_long, C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_long, C.c_void_p]),
 }
 
 _lib = None
-EXPECTED_ABI = 36  # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
+EXPECTED_ABI = 37  # = v3a_abi_version() of csrc/capi.hip; bumped together with every struct / signature change in include/vist3a_hip.h
 
 
 class HipLibraryError(RuntimeError):

@@ -1938,9 +1938,10 @@ def _splat_dicts(what: str, params: dict, m: dict, v: dict, rows: int) -> int:
     return K
 
 
-def _scene_view(args, tensors: dict, rows: int, K_plus: int, what: str, label: str) -> None:
-    """Sets the five pointers and row strides (`field`, `ld_field`) of a SplatExportArgs / SplatImportArgs from `tensors`: float32 device
-    tensors [rows, ...], sh [rows,3,K_plus], whose rows may be strided (a row's own elements contiguous).  `label` formats a name."""
+def _scene_view(args, tensors: dict, rows: int, K_plus: int, what: str, label: str, pre: str = "") -> None:
+    """Sets the five pointers and row strides (`pre` + `field`, `pre` + `ld_field`) of a SplatExportArgs / SplatImportArgs /
+    SplatTransformArgs from `tensors`: float32 device tensors [rows, ...], sh [rows,3,K_plus], whose rows may be strided (a row's own
+    elements contiguous).  `label` formats a name."""
     for field, (name, inner) in zip(L.SPLAT_FIELDS, _splat_inner(K_plus).items()):
         t, shape, width = tensors[name], (rows,) + inner, math.prod(inner)
         if not t.is_cuda or t.dtype != f32 or tuple(t.shape) != shape:
@@ -1950,8 +1951,8 @@ def _scene_view(args, tensors: dict, rows: int, K_plus: int, what: str, label: s
         ld = t.stride(0) if rows > 1 else width
         if ld < width:
             raise ValueError(f"{what}: rows of {label.format(name)} overlap (row stride {ld} < {width})")
-        setattr(args, field, t.data_ptr())
-        setattr(args, "ld_" + field, ld)
+        setattr(args, pre + field, t.data_ptr())
+        setattr(args, pre + "ld_" + field, ld)
 
 
 def mcmc_relocate(src: torch.Tensor, counts: torch.Tensor, params: dict, m: dict, v: dict, *, dst_offset: int, min_opacity: float) -> None:
@@ -2246,3 +2247,96 @@ def splat_import_splat(payload: torch.Tensor, n: int, *, quats_xyzw: bool = True
         a.payload, a.payload_bytes, a.quats_xyzw = payload.data_ptr(), payload.numel(), int(bool(quats_xyzw))
         L.check(L.load().v3a_splat_import_splat(C.byref(a), _stream()), "v3a_splat_import_splat")
     return scene, bad
+
+
+# ------------------------------------------------------------------------------------------------ scene transforms (csrc/splat_transform.hip)
+SH_BAND_COUNTS = (1, 4, 9, 16, 25)     # K + 1 of a scene that v3a_splat_transform takes: whole bands up to degree 4
+
+
+def similarity_parts(T, what: str = "similarity_parts"):
+    """A 4x4 similarity [[s R, t], [0, 1]] split on the host in fp64 -> (s, R float64 [3,3], t float64 [3]).  ValueError for what
+    is none: a bottom row other than 0 0 0 1, a non-finite entry, det <= 0 (a reflection, s <= 0) or |R R^T - I|_max > 1e-6 (shear,
+    unequal scales)."""
+    T = torch.as_tensor(T, dtype=torch.float64, device="cpu") if not isinstance(T, torch.Tensor) else T.detach().to("cpu", torch.float64)
+    if tuple(T.shape) != (4, 4) or not bool(torch.isfinite(T).all()):
+        raise ValueError(f"{what}: T must be a finite 4x4 matrix, got shape {tuple(T.shape)}")
+    if not torch.equal(T[3], torch.tensor([0.0, 0.0, 0.0, 1.0], dtype=torch.float64)):
+        raise ValueError(f"{what}: the bottom row of T must be 0 0 0 1, got {T[3].tolist()}")
+    M = T[:3, :3]
+    det = float(torch.linalg.det(M))
+    if not det > 0.0:
+        raise ValueError(f"{what}: det of the linear part is {det:g}; a similarity needs s > 0 and a proper rotation (no reflection)")
+    s = det ** (1.0 / 3.0)
+    R = M / s
+    off = float((R @ R.T - torch.eye(3, dtype=torch.float64)).abs().max())
+    if not off <= 1e-6:
+        raise ValueError(f"{what}: the linear part is not a scaled rotation (|R R^T - I|_max = {off:.3g} > 1e-6): shear or unequal scales")
+    return s, R.contiguous(), T[:3, 3].contiguous()
+
+
+def sh_rotation_matrices(R, deg: int) -> list:
+    """D_1(R) .. D_deg(R) of the rasteriser's SH basis, Y_l(R d) = D_l(R) Y_l(d), in fp64 on the host (v3a_sh_rotation_matrices;
+    no device needed) -> [float64 [2l+1, 2l+1]]"""
+    R = torch.as_tensor(R, dtype=torch.float64, device="cpu").contiguous() if not isinstance(R, torch.Tensor) else R.detach().to("cpu", torch.float64).contiguous()
+    if tuple(R.shape) != (3, 3):
+        raise ValueError(f"sh_rotation_matrices: R must be 3x3, got {tuple(R.shape)}")
+    out = torch.zeros(max(sum((2 * l + 1) ** 2 for l in range(1, max(int(deg), 0) + 1)), 1), dtype=torch.float64)
+    dp = C.POINTER(C.c_double)
+    rc = L.load().v3a_sh_rotation_matrices(C.cast(R.data_ptr(), dp), int(deg), C.cast(out.data_ptr(), dp))
+    if rc == L.V3A_OK:
+        mats, o = [], 0
+        for l in range(1, deg + 1):
+            n = 2 * l + 1
+            mats.append(out[o:o + n * n].reshape(n, n).clone())
+            o += n * n
+        return mats
+    if rc == -1:
+        raise ValueError("sh_rotation_matrices: R is not a proper rotation (|R R^T - I|_max > 1e-6 or det < 0)")
+    L.check(rc, "v3a_sh_rotation_matrices")
+
+
+def splat_transform(scene: dict, T, out: Optional[dict] = None, *, quats_xyzw: bool = True) -> dict:
+    """x' = s R x + t applied to a scene (v3a_splat_transform): `scene` as load_scene / create_splats hold it - means [U,3], scales
+    (logs) [U,3], quats [U,4], opacities (logits) [U], sh [U,3,K+1] with K + 1 in SH_BAND_COUNTS; float32 device tensors whose rows
+    may be strided.  T: a 4x4 similarity (similarity_parts; ValueError otherwise).  Means move, log-scales gain log s, quaternions
+    are multiplied by R's from the left, the harmonics' bands 1.. are rotated in the rasteriser's basis; logits and DC are copied.
+    out: None (fresh tensors), another scene dict of the same shapes, or `scene` itself (in place).  -> the five output tensors."""
+    s, R, t = similarity_parts(T, "splat_transform")
+    means, sh = scene["means"], scene["sh"]
+    if means.dim() != 2 or means.shape[1] != 3 or sh.dim() != 3 or sh.shape[1] != 3:
+        raise ValueError(f"splat_transform: means [U,3] and sh [U,3,K+1] required, got {tuple(means.shape)} and {tuple(sh.shape)}")
+    U, Kp = means.shape[0], sh.shape[2]
+    if Kp not in SH_BAND_COUNTS:
+        raise ValueError(f"splat_transform: sh holds {Kp} coefficients per channel; whole bands are required, one of {SH_BAND_COUNTS}")
+    if out is None:
+        out = {name: torch.empty((U,) + inner, device=means.device, dtype=f32) for name, inner in _splat_inner(Kp).items()}
+    a = L.SplatTransformArgs()
+    _scene_view(a, scene, U, Kp, "splat_transform", "scene[{!r}]")
+    _scene_view(a, out, U, Kp, "splat_transform", "out[{!r}]", pre="out_")
+    a.rows, a.K, a.quats_xyzw, a.scale = U, Kp - 1, int(bool(quats_xyzw)), s
+    for i, x in enumerate(R.reshape(-1).tolist()):
+        a.R[i] = x
+    for i, x in enumerate(t.tolist()):
+        a.t[i] = x
+    if U:
+        L.check(L.load().v3a_splat_transform(C.byref(a), _stream()), "v3a_splat_transform")
+    return {name: out[name] for name in SPLAT_TENSORS}
+
+
+def splat_moments(means: torch.Tensor, centre) -> torch.Tensor:
+    """Count, first and second moments of the rows of `means` (float32 device [n,3], rows may be strided) about `centre` (three host
+    floats), in fp64 and in a fixed order (v3a_splat_moments) -> float64 [10] on the device: n, sum (x - c) [3], and
+    sum (x - c)(x - c)^T as xx xy xz yy yz zz."""
+    if not means.is_cuda or means.dtype != f32 or means.dim() != 2 or means.shape[1] != 3 or (means.shape[0] > 0 and means.stride(1) != 1):
+        raise ValueError(f"splat_moments: means must be a float32 device tensor [n,3] with contiguous rows (the HIP path has no CPU fallback), got "
+                         f"{means.dtype} {tuple(means.shape)} on {means.device}")
+    n = means.shape[0]
+    ld = means.stride(0) if n > 1 else 3
+    if ld < 3:
+        raise ValueError(f"splat_moments: rows of means overlap (row stride {ld} < 3)")
+    c = (C.c_double * 3)(*[float(x) for x in (centre.tolist() if isinstance(centre, torch.Tensor) else centre)])
+    out = torch.empty(10, device=means.device, dtype=torch.float64)
+    lib = L.load()
+    ws, ws_bytes = _workspace(lib.v3a_splat_moments_workspace_bytes(n), f"v3a_splat_moments_workspace_bytes (n = {n})", means.device)
+    L.check(lib.v3a_splat_moments(_ptr(means) if n else None, ld, n, c, _ptr(out), _ptr(ws), ws_bytes, _stream()), "v3a_splat_moments")
+    return out

@@ -105,6 +105,10 @@ def inference_vist3a_argument() -> argparse.ArgumentParser:
     g.add_argument("--export_sh_rest", action="store_true",
                    help="with --export_format: write the higher-order harmonics into gaussians.compressed.ply too (default: DC colour "
                         "only, like gaussians.ply)")
+    g.add_argument("--export_frame", type=str, default="camera", choices=("camera", "normalized"),
+                   help="the frame of gaussians.ply and of every --export_format file: camera (the first camera's OpenCV frame, as "
+                        "predicted) or normalized (upright, centred, unit-sized: world_normalisation of the predicted or pose-refined "
+                        "cameras and the means, moved on the GPU, harmonics rotated; writes world_transform.json; the videos keep the camera frame)")
     g.add_argument("--lpips_vgg_weights", type=str, default=None, metavar="PATH",
                    help="with --post_opt_eval_every: torchvision's VGG-16 state dict (vgg16-397923af.pth); with --lpips_lin_weights adds "
                         "LPIPS to post_opt_stats.json")

@@ -3,7 +3,8 @@ this package's own gaussians.ply), `ply_compressed` (SuperSplat) and `splat` (an
 The host parses the text header into a column table and uploads the payload once; every value is decoded on the device
 (csrc/splat_import.hip); the number of rows that decoded to a NaN or Inf is the one value read back.
 
-    python -m vist3a_amd.utils.splat_import IN --out OUT --to {ply,splat,ply_compressed} [--opacity linear|logit] [--dc_only]"""
+    python -m vist3a_amd.utils.splat_import IN --out OUT --to {ply,splat,ply_compressed} [--opacity linear|logit] [--dc_only]
+                                            [--transform FILE.json] [--align_principal_axes]"""
 from __future__ import annotations
 
 import argparse
@@ -182,10 +183,20 @@ def main(argv=None) -> int:
     ap.add_argument("--to", required=True, choices=FORMATS)
     ap.add_argument("--opacity", default="logit", choices=("linear", "logit"), help="how a float PLY input stores its opacity (gaussians.ply: linear)")
     ap.add_argument("--dc_only", action="store_true", help="write the DC colour only")
+    ap.add_argument("--transform", default=None, metavar="FILE.json",
+                    help="move the scene by a 4x4 similarity before writing it: a JSON matrix, or a world_transform.json (its `transform`)")
+    ap.add_argument("--align_principal_axes", action="store_true",
+                    help="then centre the scene on the median of its means and turn its principal axes onto x, y, z (descending variance)")
     args = ap.parse_args(argv)
     scene = load_scene(args.input, opacity=args.opacity, quats_xyzw=True)
     if args.dc_only:
         scene["sh"] = scene["sh"][..., :1].contiguous()
+    if args.transform or args.align_principal_axes:      # on the device, harmonics rotated (csrc/splat_transform.hip)
+        from .splat_transform import align_principal_axes, read_transform, transform_scene
+        if args.transform:
+            scene = transform_scene(scene, read_transform(args.transform), scene)
+        if args.align_principal_axes:
+            scene = transform_scene(scene, align_principal_axes(scene["means"]), scene)
     data = export_scene(scene, args.to, args.out, quats_xyzw=True)
     print(f"{args.out}: {len(data)} bytes, {args.to}")
     return 0
