@@ -8,10 +8,13 @@ ROOT = Path(__file__).resolve().parents[1]
 _SIZES = {"char": 1, "int": 4, "float": 4, "long": 8, "long long": 8, "double": 8}
 
 
-def c_layout(name: str):
-    """{field: (offset, size)} and the total size of the typedef struct `name` (pointers and longs 8 bytes, ints 4, natural
-    alignment)"""
-    txt = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "vist3a_hip.h").read_text(), flags=re.S)
+def header_text() -> str:
+    """include/vist3a_hip.h without its comments"""
+    return re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "vist3a_hip.h").read_text(), flags=re.S)
+
+
+def _layout(txt: str, name: str):
+    """({field: (offset, size)}, size, alignment) of the typedef struct `name`"""
     body = re.search(r"typedef struct \{([^}]*)\}\s*" + name + r"\s*;", txt).group(1)
     off, fields, biggest = 0, {}, 1
     for decl in (d.strip() for d in body.split(";")):
@@ -19,16 +22,29 @@ def c_layout(name: str):
             continue
         first, *more = [p.strip() for p in decl.split(",")]
         base = first[:re.search(r"[\w\[\]]+$", first).start()].strip()            # the type in front of the first declarator
+        scalar = base.replace("const", "").replace("unsigned", "").strip() or "int"
         for d in [first[len(base):].strip()] + more:
             pointer = d.startswith("*") or base.endswith("*")
             m = re.fullmatch(r"\*?\s*(\w+)(?:\[(\d+)\])?", d)
-            size = 8 if pointer else _SIZES[base.replace("const", "").replace("unsigned", "").strip() or "int"]
+            if pointer:
+                size = align = 8
+            elif scalar in _SIZES:
+                size = align = _SIZES[scalar]
+            else:                                                                 # an earlier typedef struct of the header, embedded
+                _, size, align = _layout(txt, scalar)
             count = int(m.group(2) or 1)
-            off = (off + size - 1) // size * size
+            off = (off + align - 1) // align * align
             fields[m.group(1)] = (off, size * count)
             off += size * count
-            biggest = max(biggest, size)
-    return fields, (off + biggest - 1) // biggest * biggest
+            biggest = max(biggest, align)
+    return fields, (off + biggest - 1) // biggest * biggest, biggest
+
+
+def c_layout(name: str):
+    """{field: (offset, size)} and the total size of the typedef struct `name` (pointers and longs 8 bytes, ints 4, natural
+    alignment; a field whose type is another struct of the header has that struct's size and alignment)"""
+    fields, size, _ = _layout(header_text(), name)
+    return fields, size
 
 
 def assert_mirrors(struct, name: str) -> None:

@@ -653,13 +653,11 @@ def post_optimize(gaussians: Gaussians, images: torch.Tensor, extrinsics: torch.
             cov, op = ops.splat_activate(p["scales"], p["quats"], p["opacities"])
             if pose:
                 view_j, campos_j = ops.camera_adjust(w2c_base[j], c2w_base[j], splats["pose_deltas"][gj])
-                color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view_j, campos_j, Kpix[j], W, H,
-                                            sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
-                                            clamp_rgb=True, workspace=ws, rasterize_mode=mode, camera_grad=True, **extra)
             else:
-                color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view[j], campos[j], Kpix[j], W, H,
-                                            sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
-                                            clamp_rgb=True, workspace=ws, rasterize_mode=mode, **extra)
+                view_j, campos_j = view[j], campos[j]
+            color, depth, alpha = ops.gs_render(p["means"], cov, p["sh"], op, view_j, campos_j, Kpix[j], W, H,
+                                                sh_degree=sh_degree, sh_layout=1, background=background if bkgds is None else bkgds[i],
+                                                clamp_rgb=True, workspace=ws, rasterize_mode=mode, camera_grad=pose, **extra)
             if bil:
                 color = ops.bilagrid_slice(color, splats["bil_grids"][gj])
             loss, l1, ssim = ops.photometric_loss(color, images[j], cfg.ssim_lambda)
